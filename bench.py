@@ -15,10 +15,16 @@ configs[3] at any G); a rank then encodes its share in batches of at most --batc
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts torchrun itself (a child
 process launched before anything touches the GPU) and relays its output and exit code.
 
-Printed (rank 0, one JSON line): the metric, `roofline` for the dominant kernel (algorithmic bytes per
-launch / average launch time measured with HIP events on the codec's stream during the timed steps),
-and `cpu_baseline`: the reference's own src/encoders (oracle/_ref/libbraref.so, compiled from the
-reference sources) timed on this host, single-threaded and on all the cores this box gives us.
+A plain run sets up, warms up, times the steps and prints (rank 0, one JSON line) the metric with
+`ms_per_step`, the workload and the compressed sizes of the last step.  `--dump-outputs DIR` also
+writes what the last timed step computed (see dump_outputs) so that two builds can be compared.
+
+`--full` adds everything else, each a run of its own outside the timed region except the HIP-event
+kernel timing: `roofline` for the dominant kernel (algorithmic bytes per launch / average launch
+time measured with HIP events on the codec's stream during the timed steps), the per-stage times,
+the round-trip and reference checks, the decode and transfer-inclusive figures, the measured copy
+peak, and `cpu_baseline`: the reference's own src/encoders (oracle/_ref/libbraref.so, compiled from
+the reference sources) timed on this host, single-threaded and on all the cores it gives us.
 """
 import argparse
 import importlib
@@ -55,17 +61,27 @@ def parse():
     ap.add_argument("--bytes-per-gpu", type=int, default=256 << 20, help="weak scaling: input bytes per rank")
     ap.add_argument("--total-bytes", type=int, default=0, help="strong scaling: global input bytes (e.g. 2147483648)")
     ap.add_argument("--batch-bytes", type=int, default=256 << 20, help="largest batch one encode call takes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's assembled chunk stream) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also: kernel timing and roofline, round-trip and reference checks, decode and transfer-inclusive "
+                         "figures, copy peak, CPU baseline (the options below narrow it)")
     ap.add_argument("--cpu-threads", type=int, default=CPU_SHARE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--profile-all", action="store_true", help="time every kernel during the timed steps")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the decode and PCIe-inclusive measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full without the round-trip and reference checks")
+    ap.add_argument("--profile-all", action="store_true", help="--full: time every kernel during the timed steps")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the decode and PCIe-inclusive measurements")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
     ap.add_argument("--gather-mode", default="exact", choices=["exact", "bound"],
                     help="N > 1: payloads gathered at their exact sizes (one size all_gather per step) or at the geometry's bound")
     ap.add_argument("--pcie-batches", type=int, default=4, help="batches of the split transfer-inclusive encode (two contexts)")
     ap.add_argument("--pcie-stream", type=int, default=4, help="batches of the streamed transfer-inclusive encode (pipelined API)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.profile_all and not args.full:
+        ap.error("--profile-all needs --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_torchrun(args) -> int:
@@ -428,6 +444,57 @@ def pcie_stream(bra, codec, data_np, kind, bs, nstream):
     return res
 
 
+DUMP_PAYLOAD_MAX = 8 << 20  # payload bytes written: all of a smaller payload, else a seeded sample of this many
+DUMP_SEED = 0x62726131
+
+
+def dump_outputs(path, H, O, P, crc, nbg):
+    """Write the assembled chunk stream of the last timed step (what a caller of the timed path
+    receives on rank 0) as DIR/<name>.npy, about 35 MB at the most:
+
+      headers.npy             float32 [nbg, 268]  the in-memory chunk headers, every byte
+      offsets.npy             float64 [nbg + 1]   payload offsets (exact: far below 2^53)
+      crc32c.npy              float64 [1]         the merged chunk-stream CRC32C
+      payload.npy             float32             the payload bytes up to offsets[nbg] when there are at
+                                                  most DUMP_PAYLOAD_MAX of them, else the bytes at
+                                                  DUMP_PAYLOAD_MAX sorted positions drawn once from
+                                                  numpy's default_rng(DUMP_SEED) over [0, offsets[nbg])
+      payload_block_sums.npy  float64 [nbg, 2]    per block, over all of its payload bytes: their sum and
+                                                  their sum weighted by (position in the payload mod
+                                                  65521) + 1, so that every payload byte takes part
+
+    The inputs are synthetic and fixed by the arguments, so two builds run with the same arguments
+    can be compared array for array."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    off = O[: nbg + 1]
+    n = int(off[nbg].item())
+    pay = P[:n]
+    if n > DUMP_PAYLOAD_MAX:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_PAYLOAD_MAX, dtype=np.int64))
+        sample = pay[torch.from_numpy(idx).to(pay.device)]
+    else:
+        sample = pay
+    v = pay.to(torch.int64)
+    w = torch.arange(n, dtype=torch.int64, device=pay.device) % 65521 + 1
+    zero = torch.zeros((1,), dtype=torch.int64, device=pay.device)
+    sums = []
+    for x in (v, v * w):  # block sums as differences of the running sum at the block offsets (below 2^53)
+        run = torch.cat([zero, torch.cumsum(x, 0)])
+        sums.append(run[off[1:]] - run[off[:-1]])
+    arrays = {
+        "headers": H[:nbg].to(torch.float32),
+        "offsets": off.to(torch.float64),
+        "crc32c": (crc.reshape(1).to(torch.int64) & 0xFFFFFFFF).to(torch.float64),
+        "payload": sample.to(torch.float32),
+        "payload_block_sums": torch.stack(sums, 1).to(torch.float64),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -541,25 +608,33 @@ def main():
         if prev is not None:
             gather_assemble(*prev)
 
-    # ---- find the dominant kernel (one untimed, fully profiled pass) ----
-    kernel_slots = [s for s in codec.SLOTS if not s.startswith(("stage.", "dec."))]
-    enc_slots = [s for s in codec.SLOTS if not s.startswith("dec.")]
-    codec.prof_enable(codec.slot_mask(*enc_slots))
-    step()
-    flush()
-    torch.cuda.synchronize()
-    prof0 = codec.prof_read()
-    kernel_slots = [s for s in kernel_slots if s in prof0]  # (a library built before a slot existed reports fewer)
-    dominant = max(kernel_slots, key=lambda s: prof0[s][0])
-    stage_slots = [s for s in codec.SLOTS if s.startswith("stage.")]
-    timed_slots = enc_slots if args.profile_all else (dominant, *stage_slots)
-    codec.prof_enable(codec.slot_mask(*timed_slots))
+    if args.full:
+        # ---- find the dominant kernel (one untimed, fully profiled pass) ----
+        kernel_slots = [s for s in codec.SLOTS if not s.startswith(("stage.", "dec."))]
+        enc_slots = [s for s in codec.SLOTS if not s.startswith("dec.")]
+        codec.prof_enable(codec.slot_mask(*enc_slots))
+        step()
+        flush()
+        torch.cuda.synchronize()
+        prof0 = codec.prof_read()
+        kernel_slots = [s for s in kernel_slots if s in prof0]  # (a library built before a slot existed reports fewer)
+        dominant = max(kernel_slots, key=lambda s: prof0[s][0])
+        stage_slots = [s for s in codec.SLOTS if s.startswith("stage.")]
+        timed_slots = enc_slots if args.profile_all else (dominant, *stage_slots)
+        codec.prof_enable(codec.slot_mask(*timed_slots))
 
     for _ in range(args.warmup):
         step()
     flush()
     torch.cuda.synchronize()
-    codec.prof_reset()
+    if args.full:
+        codec.prof_reset()
+
+    def finish():
+        codec.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
 
     # ---- timed region ----
     if world > 1:
@@ -576,27 +651,30 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    prof = codec.prof_read()
-
     value = global_total * args.steps / elapsed / 1e9
     ms_per_step = elapsed / args.steps * 1e3
-    dms, dcnt, dbytes = prof[dominant]
-    avg_ms = dms / max(1, dcnt)
-    bytes_per_launch = dbytes / max(1, dcnt)
-    achieved = bytes_per_launch / (avg_ms / 1e3) / 1e9 if avg_ms > 0 else 0.0
+    if args.full:
+        prof = codec.prof_read()
+        dms, dcnt, dbytes = prof[dominant]
+        avg_ms = dms / max(1, dcnt)
+        bytes_per_launch = dbytes / max(1, dcnt)
+        achieved = bytes_per_launch / (avg_ms / 1e3) / 1e9 if avg_ms > 0 else 0.0
 
     line = None
     if rank == 0:
         H, O, P = result["stream"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, H, O, P, result["crc_t"], nbg)
         result["crc"] = int(result["crc_t"].item()) & 0xFFFFFFFF
         off_h = O.cpu().numpy()
         hdr_h = H.cpu().numpy()
         payload_bytes = int(off_h[nbg])
         rle_bytes = int(hdr_h[:, 260:264].copy().view(np.uint32).sum())
         pipeline_alg = 14 * global_total + 3 * rle_bytes + payload_bytes + 267 * nbg  # SURVEY 8.1 row d
-        stage_ms = {s.split(".")[1]: round(prof[s][0] / args.steps, 3) for s in stage_slots}  # device ms per step (a stage may open several scopes per step)
         check, secondary = None, {}
-        if not args.no_check:
+        if args.full:
+            stage_ms = {s.split(".")[1]: round(prof[s][0] / args.steps, 3) for s in stage_slots}  # device ms per step (a stage may open several scopes per step)
+        if args.full and not args.no_check:
             # decode the assembled global stream; its chunk-stream CRC must equal the merged shares
             # (every rank's input took part), and the blocks this rank holds must come back exactly
             out = codec.decode(H, O, P, global_total, bs)
@@ -631,7 +709,7 @@ def main():
                     "algorithmic_bytes_per_launch": int(dp[dk][2] / max(1, dp[dk][1])),
                     "kernels_ms": {s: round(dp[s][0] / max(1, dp[s][1]), 4) for s in codec.DECODE_KERNELS}}
             del out
-        if not args.no_secondary and world == 1 and len(batches) == 1:
+        if args.full and not args.no_secondary and world == 1 and len(batches) == 1:
             codec2 = bra.BlockCodec(local)
             secondary.update(pcie_inclusive(codec, data_np, d, bs, nb, hdr, off, pay, payload_bytes, work_stream, args.pcie_batches, codec2))
             codec2.close()
@@ -674,10 +752,10 @@ def main():
                 "avg_launch_ms": round(avg_ms, 4),
                 "launches": dcnt,
                 "algorithmic_bytes_per_launch": int(bytes_per_launch),
-            },
+            } if args.full else None,
             "pipeline": {
-                "stage_ms": stage_ms,
-                "encode_device_ms": round(sum(stage_ms.values()), 3),
+                "stage_ms": stage_ms if args.full else None,
+                "encode_device_ms": round(sum(stage_ms.values()), 3) if args.full else None,
                 "algorithmic_bytes": pipeline_alg,
                 "hbm_frac": round(pipeline_alg / (ms_per_step / 1e3) / (HBM_PEAK_GBS * 1e9), 4),
                 "ratio": round((payload_bytes + 267 * nbg) / global_total, 4),
@@ -693,6 +771,9 @@ def main():
             # payloads at their exact sizes or at the geometry's bound, --gather-mode)
             line["gather_bytes_per_step"] = int(gather.last_bytes)
             line["gather_mode"] = args.gather_mode
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            return finish()
         if args.profile_all:
             line["kernels"] = {k: {"ms": round(v[0] / max(1, v[1]), 4), "launches": v[1], "GBps": round(v[2] / max(v[0], 1e-9) / 1e6, 1)}
                                for k, v in prof.items() if v[1]}
@@ -745,10 +826,7 @@ def main():
                 gpu_chunks.append((pi, lens, osz, esz, pay_h[off_h[b]:off_h[b] + esz].tobytes()))
             line["cpu_baseline"] = cpu_baseline(data_np, bs, args.cpu_threads, gpu_chunks)
         print(json.dumps(line), flush=True)
-    codec.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in default "$@"; do
     L=$PWD/br-archive_amd/libbra_hip.so; E=BRA_AB_NONE=1
     case $v in default) ;; env:*) E=${v#env:} ;; *) L=$PWD/br-archive_amd/build/variants/$v/libbra_hip.so ;; esac
-    env $E BRA_HIP_LIB=$L timeout -k 10 200 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-check --profile-all ${BENCH_ARGS:-} > $O/bench_${v}_$rep.json 2>> $O/bench.err
+    env $E BRA_HIP_LIB=$L timeout -k 10 200 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-check --profile-all ${BENCH_ARGS:-} > $O/bench_${v}_$rep.json 2>> $O/bench.err
     rc=$?; [ $rc -eq 0 ] || { echo "bench $v rc $rc"; exit $rc; }
     python3 scripts/show_bench.py $O/bench_${v}_$rep.json | head -${SHOW_LINES:-40} | sed "s/^/[$v $rep] /"
   done

@@ -23,17 +23,17 @@ if has smoke; then
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; step smoke $?
 fi
 if has bench; then
-  timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; step bench $?
+  timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; step bench $?
   tail -c 600 $O/bench.json
 fi
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 if has prof; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $O/prof_bench.json 2> $O/prof.err; step prof $?
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $O/prof_bench.json 2> $O/prof.err; step prof $?
 fi
 if has pmc; then
   for w in ${PMC_WORKLOADS:-text:1048576 random:1048576 sym16:8388608}; do
     k=${w%%:*}; bs=${w#*:}
-    B1="python3 bench.py --steps 2 --warmup 0 --no-cpu-baseline --no-check --no-secondary --kind $k --block-size $bs"
+    B1="python3 bench.py --full --steps 2 --warmup 0 --no-cpu-baseline --no-check --no-secondary --kind $k --block-size $bs"
     D=$O/pmc_${k}_$bs
     timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $D/fetch -o run --output-format csv -- $B1 > $D.fetch.log 2>&1; step "pmc fetch $k" $?
     timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $D/write -o run --output-format csv -- $B1 > $D.write.log 2>&1; step "pmc write $k" $?

@@ -1,4 +1,4 @@
-"""Generate tests/golden/golden.npz from the REFERENCE encoders.
+"""Generate tests/golden/golden.npz and golden_random64k.npz from the REFERENCE encoders.
 
 Run in the build container (where /root/reference exists):
     make -C oracle && python tests/golden/make_golden.py
@@ -70,6 +70,9 @@ def cases(lib, skip_cfg1: bool):
         yield "cfg1_tiled_65536", synth(lib, 3, 0, 65536)
 
 
+RANDOM_64K = ("random_65535", "random_65536")
+
+
 def main():
     if not have_ref():
         sys.exit("oracle/_ref/libbraref.so missing: run `make -C oracle ref` with /root/reference present")
@@ -93,10 +96,14 @@ def main():
         names.append(name)
         print(f"{name:24s} n={len(data):6d} pi={ch.primary_index:6d} rle={len(ch.rle):6d} "
               f"payload={ch.encoded_size:6d}  ({time.time() - t:.2f}s)", flush=True)
-    arrays["names"] = np.array(names)
-    out = os.path.join(ROOT, "tests", "golden", "golden.npz")
-    np.savez_compressed(out, **arrays)
-    print("wrote", out, os.path.getsize(out), "bytes")
+    # two archives, each below 1 MiB: the 64 KiB random cases do not compress and get their own
+    # (tests/conftest.py load_golden reads both)
+    for fname, pick in (("golden.npz", lambda n: n not in RANDOM_64K), ("golden_random64k.npz", lambda n: n in RANDOM_64K)):
+        part = {k: v for k, v in arrays.items() if pick(k.split("/")[0])}
+        part["names"] = np.array([n for n in names if pick(n)])
+        out = os.path.join(ROOT, "tests", "golden", fname)
+        np.savez_compressed(out, **part)
+        print("wrote", out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_sharded_path_on_one_gpu(world):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-secondary", "--bytes-per-gpu", str(64 << 20)]
+           "--full", "--no-cpu-baseline", "--no-secondary", "--bytes-per-gpu", str(64 << 20)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -586,6 +586,17 @@ class BlockCodec:
             raise RuntimeError("bra_gpu_debug_rerun_jobs failed")
         return r
 
+    def debug_bwt_path(self):
+        """(path, max_bins) of the last encode's first BWT split: path 1 = wide (rotations placed by
+        two packed key bytes at once), 0 = the 8-bit level 0; max_bins = the largest number of
+        distinct 16-bit packed prefixes in one block (0 when the prefix maps were not built)."""
+        f = lib.bra_gpu_debug_bwt_path
+        f.argtypes, f.restype = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], C.c_int
+        p, b = C.c_uint(0), C.c_uint(0)
+        if f(self.ctx, C.byref(p), C.byref(b)) != 0:
+            raise RuntimeError("bra_gpu_debug_bwt_path failed")
+        return int(p.value), int(b.value)
+
     def stage_ptr(self, stage: int) -> int:
         return lib.bra_gpu_stage_ptr(self.ctx, stage) or 0
 

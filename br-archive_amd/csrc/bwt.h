@@ -19,6 +19,9 @@ const uint32_t* bwt_sa(const BwtWorkspace* w);
 // Valid only right after an encode whose input the caller still holds; -1 otherwise.
 int  bwt_debug_rerun_jobs(BwtWorkspace* w, int reps, hipStream_t s, uint32_t shuffle_seed);
 void bwt_forget_jobs(BwtWorkspace* w);  // any other call on the context invalidates the re-run state
+// Diagnostics: the last encode's first split (1: wide, by two packed key bytes; 0: the 8-bit level 0)
+// and the largest count of distinct 16-bit packed prefixes in one of its blocks.
+void bwt_last_path(const BwtWorkspace* w, uint32_t* path, uint32_t* max_bins);
 
 // BWT of every block: d_L[off..off+len) = last column, d_pi[b] = primary index (block-local).
 bool bwt_encode_device(BwtWorkspace* w, const uint8_t* d_in, const BlockDesc* d_blocks, const BlockDesc* h_blocks, uint32_t nblocks,

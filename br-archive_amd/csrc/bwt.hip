@@ -255,7 +255,8 @@ __device__ __forceinline__ uint64_t p_make(const uint8_t* __restrict__ pk, uint3
 // n_tiles_next, and the byte-accounting counts).  Every slot is zeroed once, by k_ctr_init at the
 // start of the call (or of a fallback round), so no kernel ever resets a counter a later kernel
 // reads, and the host never has to copy a level's counts back before it launches the next level.
-constexpr uint32_t MAX_LEVELS = DCAP_BIG + 2;  // slot 0 + one per STRING level (depth <= DCAP_BIG)
+constexpr uint32_t MAX_LEVELS = DCAP_BIG + 3;  // slot 0 + one per STRING level (depth <= DCAP_BIG) + the wide split's path slot
+constexpr uint32_t L0W_SLOT   = MAX_LEVELS - 1;  // n_big: the call's largest prefix count B; n_tiles_next: blocks outside [2, L0W_MAX_BINS]
 
 __global__ void k_ctr_init(Counters* ctr, uint32_t nslots)
 {
@@ -737,6 +738,12 @@ struct ScanArgs
     const PackDesc* pk;        // STRING: packed key strings per block
     const uint32_t* btot;      // level 0: per-bucket digit totals (k_l0_colscan) instead of the tile rows
     uint32_t*       bbase;     // level 0: per-bucket sub-bucket starts (| NEXT_FLAG), added to the tiles' running counts by the scatter
+    // wide first split (compact rows): bucket bi = (block bi / 256, first key byte bi % 256) at depth 1;
+    // btot / bbase hold wstride entries per block, one per non-empty 16-bit prefix in prefix order
+    // (dense index = rank of the prefix in the block's presence bitmap)
+    const uint32_t* wbm;       // presence bitmaps, L0W_BMW words per block (null: rows of 256 digits)
+    const uint16_t* wrk;       // dense index of each bitmap word's first bit
+    uint32_t        wstride;
 };
 
 // One wave per bucket (SCAN_WAVES buckets per workgroup), lane = 4 consecutive digits.  Sub-bucket offsets
@@ -780,7 +787,20 @@ __global__ void __launch_bounds__(64 * SCAN_WAVES) k_scan(ScanArgs a)
         const uint32_t ntiles = (active && !a.btot) ? div_up(B.len, TILE) : 0;
         const uint4*   th     = reinterpret_cast<const uint4*>(a.tile_hist + (size_t) B.tile0 * 256) + lane;
         uint32_t       tot[4] = {0, 0, 0, 0};
-        if (a.btot && active)
+        uint32_t       wdn[4] = {~0u, ~0u, ~0u, ~0u};  // compact rows: the dense index of each digit's prefix (~0: empty)
+        if (a.wbm && active)
+        {
+            const uint32_t wi = B.block * 2048u + (bi & 255u) * 8u + ((uint32_t) lane >> 3), sh = ((uint32_t) lane & 7u) * 4u;
+            const uint32_t word = a.wbm[wi], rk = a.wrk[wi];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((word >> (sh + r)) & 1u)
+                {
+                    wdn[r] = rk + __popc(word & ((1u << (sh + r)) - 1u));
+                    tot[r] = a.btot[(size_t) B.block * a.wstride + wdn[r]];
+                }
+        }
+        else if (a.btot && active)
         {
             const uint4 q = reinterpret_cast<const uint4*>(a.btot + (size_t) bi * 256)[lane];
             tot[0] = q.x, tot[1] = q.y, tot[2] = q.z, tot[3] = q.w;
@@ -825,7 +845,14 @@ __global__ void __launch_bounds__(64 * SCAN_WAVES) k_scan(ScanArgs a)
             }
             uint4*   to     = reinterpret_cast<uint4*>(a.tile_off + (size_t) B.tile0 * 256) + lane;
             uint32_t run[4] = {B.start + base[0], B.start + base[1], B.start + base[2], B.start + base[3]};
-            if (a.bbase && active)
+            if (a.wbm && active)
+            {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (wdn[r] != ~0u)
+                        a.bbase[(size_t) B.block * a.wstride + wdn[r]] = run[r] | flag[r];
+            }
+            else if (a.bbase && active)
                 reinterpret_cast<uint4*>(a.bbase + (size_t) bi * 256)[lane] =
                     make_uint4(run[0] | flag[0], run[1] | flag[1], run[2] | flag[2], run[3] | flag[3]);
             for (uint32_t t = 0; t < ntiles; ++t)
@@ -843,7 +870,7 @@ __global__ void __launch_bounds__(64 * SCAN_WAVES) k_scan(ScanArgs a)
         // not move but continues needs its payloads re-gathered in place when they run out (nomove
         // code 2), otherwise it is left alone (code 1)
         const bool     regather = (MODE == MODE_STRING) && (B.buf == 2u || B.d + 1 - B.kd >= CARRY);
-        const uint32_t kd       = (MODE == MODE_STRING) ? (B.buf == 2u ? 1u : (regather ? B.d + 1 : B.kd)) : eff_kd(B, MODE);
+        const uint32_t kd       = (MODE == MODE_STRING) ? (regather ? B.d + 1 : B.kd) : eff_kd(B, MODE);  // buf 2 (depth 0, or 1 after the wide split): d + 1
         bool nm_next = false;
         if (MODE == MODE_STRING && nomove && regather)
         {
@@ -868,7 +895,7 @@ __global__ void __launch_bounds__(64 * SCAN_WAVES) k_scan(ScanArgs a)
         // STRING: a bucket that stays in place as one fallback group (code 3) has its payloads' low
         // words copied to p32 by the scatter, where the group flush reads them
         nm_fin = MODE == MODE_STRING && nomove && __any(nm_fin);
-        if (active && lane == 0)
+        if (active && lane == 0 && !a.wbm)  // (the scatters that read the packed input move everything)
             a.nomove[bi] = nomove ? (nm_fin ? 3 : (nm_next ? 2 : 1)) : 0;
         // ---- wave jobs: greedy packing of consecutive sub-buckets of <= JOB_MAX elements ----
         // The non-empty sub-buckets form a list in digit order; a wave-job sub-bucket weighs its
@@ -1385,6 +1412,380 @@ __global__ void __launch_bounds__(TPB) k_l0_scatter(const uint8_t* __restrict__ 
             }
         }
         __syncthreads();
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+// Wide first split: every rotation is placed by its first TWO key bytes in one pass, so slot 1 starts
+// with depth-2 buckets and MSD level 1 (a second move of nearly every element) does not exist.  It
+// applies when the 16-bit prefixes of every block of the call are sparse (2 <= B <= L0W_MAX_BINS
+// non-empty ones: text 2.4 K, 16-symbol data 5.5 K per MiB; uniform random bytes have all 65536 and
+// keep the 8-bit level 0).  The non-empty prefixes of a block map, order-preserving, onto dense bins
+// 0..B-1 through a presence bitmap (k_l0w_bins) and a per-word rank table (k_l0w_rank):
+// dense(p) = rank(bitmap, p).  A tile is L0W_TILE consecutive rotations, large enough that its run
+// into one prefix's sub-bucket is ~11 elements on text (4 Ki-element tiles: 4, the stores do not
+// coalesce; scripts/wide_l0.py).  k_l0w_hist counts a tile's dense bins (16-bit rows), k_l0w_colscan
+// turns a block's rows into running offsets and bin totals, k_l0w_buckets makes one depth-1 bucket
+// per (block, first byte) and k_scan handles them as it handles level-1 buckets (compact rows:
+// ScanArgs.wbm).  k_l0w_scatter counting-sorts the tile in LDS as 2-byte tile-local positions and
+// stores run by run; payload, digit byte and job word are rebuilt from the packed window.
+// -------------------------------------------------------------------------------------------------
+constexpr uint32_t L0W_TILE     = 16384;
+constexpr uint32_t L0W_THREADS  = 1024;
+constexpr uint32_t L0W_PT       = L0W_TILE / L0W_THREADS;
+constexpr uint32_t L0W_MAX_BINS = 8192;
+constexpr uint32_t L0W_GIVE_UP  = L0W_MAX_BINS + 512;  // prefixes seen beyond which a block is not looked at further (k_l0w_bins)
+constexpr uint32_t L0W_BMW      = 2048;  // 65536-bit presence bitmap, in words
+constexpr uint32_t L0W_WIN      = L0W_TILE + 64;  // window bytes (8 bits per character at most)
+
+__device__ __forceinline__ void l0w_load_window(const uint8_t* __restrict__ pk, uint32_t start, uint32_t cnt, uint32_t b, uint8_t* win)
+{
+    const uint4*   src = reinterpret_cast<const uint4*>(pk + (start * b) / 8);  // tile starts are multiples of 16 characters
+    const uint32_t nq  = ((cnt * b + 7) / 8 + 16 + 15) / 16;
+    for (uint32_t i = threadIdx.x; i < nq; i += L0W_THREADS)
+        reinterpret_cast<uint4*>(win)[i] = src[i];
+}
+
+__device__ __forceinline__ uint32_t l0w_dense(const uint32_t* bm, const uint16_t* rk, uint32_t p)
+{
+    return rk[p >> 5] + __popc(bm[p >> 5] & ((1u << (p & 31)) - 1u));
+}
+
+// Presence bitmap of the 16-bit prefixes of every block (bm and over zeroed by the caller), in two
+// launches: phase 0 takes the first tile of every block, phase 1 the others.  A tile adds only the
+// words that still lack some of its bits (same-address device atomics from the 64 tiles of a block
+// serialise; after a few tiles the block's bitmap has nearly every bit the later tiles bring).  A
+// block is given up -- marked in `over`, its later tiles return at once -- as soon as a tile sees
+// more than L0W_GIVE_UP prefixes in its own bits and the block's so far: uniform random bytes after
+// the first tile (~14.5 K of its 16 Ki positions), 16-symbol data in 8 MiB blocks after a few.  Blocks
+// with up to L0W_GIVE_UP prefixes get their exact count.
+__global__ void __launch_bounds__(L0W_THREADS) k_l0w_bins(const uint8_t* __restrict__ packed, const BlockDesc* __restrict__ blocks,
+                                                          const PackDesc* __restrict__ pkd, const L0Tile* __restrict__ tiles, uint32_t ntiles,
+                                                          const uint32_t* __restrict__ wt0, uint32_t phase, uint32_t* bm, uint32_t* over)
+{
+    __shared__ uint32_t bm_s[L0W_BMW];
+    __shared__ uint32_t npre;
+    __shared__ __attribute__((aligned(16))) uint8_t win[L0W_WIN];
+    const uint32_t t = phase ? blockIdx.x : wt0[blockIdx.x];
+    if (t >= ntiles)
+        return;
+    const L0Tile T = tiles[t];
+    if (phase && (T.start == 0 || dev_count(&over[T.block])))
+        return;
+    const PackDesc P   = pkd[T.block];
+    const uint32_t cnt = min(L0W_TILE, blocks[T.block].len - T.start);
+    l0w_load_window(packed + P.poff, T.start, cnt, P.b, win);
+    for (uint32_t i = threadIdx.x; i < L0W_BMW; i += L0W_THREADS)
+        bm_s[i] = 0;
+    if (threadIdx.x == 0)
+        npre = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < L0W_PT; ++i)
+    {
+        const uint32_t e = threadIdx.x + i * L0W_THREADS;
+        if (e < cnt)
+        {
+            const uint32_t p = (uint32_t) (win_bits64(win, e * P.b) >> 48);
+            atomicOr(&bm_s[p >> 5], 1u << (p & 31));
+        }
+    }
+    __syncthreads();
+    {
+        uint32_t c = 0;
+        for (uint32_t i = threadIdx.x; i < L0W_BMW; i += L0W_THREADS)
+        {
+            uint32_t*      g    = bm + (size_t) T.block * L0W_BMW + i;
+            const uint32_t mine = bm_s[i], have = dev_count(g);  // (a stale word only costs an atomic)
+            c += __popc(mine | have);
+            if (mine & ~have)
+                atomicOr(g, mine);
+        }
+        for (int d = 32; d >= 1; d >>= 1)
+            c += __shfl_xor(c, d, WAVE);
+        if ((threadIdx.x & 63) == 0)
+            atomicAdd(&npre, c);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && npre > L0W_GIVE_UP)
+        __hip_atomic_store(&over[T.block], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// rank table and B of every block; into the path slot: n_big = the call's largest B, n_tiles_next = the
+// widest character of its blocks in bits (sizes the LDS windows), bit 31 set when a block's B is
+// outside [2, L0W_MAX_BINS]
+__global__ void __launch_bounds__(1024) k_l0w_rank(const uint32_t* __restrict__ bm, const uint32_t* __restrict__ over, const PackDesc* __restrict__ pkd,
+                                                   uint16_t* __restrict__ rk, Counters* __restrict__ slot)
+{
+    __shared__ uint32_t wsum[16];
+    const uint32_t  block = blockIdx.x, i = threadIdx.x, lane = i & 63, wv = i >> 6;
+    const uint32_t* g     = bm + (size_t) block * L0W_BMW;
+    const uint32_t  c0 = __popc(g[2 * i]), c1 = __popc(g[2 * i + 1]);
+    uint32_t        x = c0 + c1;
+    for (int d = 1; d < 64; d <<= 1)
+    {
+        const uint32_t y = __shfl_up(x, d, WAVE);
+        if ((int) lane >= d)
+            x += y;
+    }
+    if (lane == 63)
+        wsum[wv] = x;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+    for (uint32_t k = 0; k < 16; ++k)
+    {
+        base += k < wv ? wsum[k] : 0;
+        tot += wsum[k];
+    }
+    const uint32_t ex = base + x - c0 - c1;  // < 65536 wherever a bit follows
+    rk[(size_t) block * L0W_BMW + 2 * i]     = (uint16_t) ex;
+    rk[(size_t) block * L0W_BMW + 2 * i + 1] = (uint16_t) (ex + c0);
+    if (i == 0)
+    {
+        if (over[block])  // a tile gave the block up: its bitmap is partial, the count a lower bound
+            tot = max(tot, L0W_GIVE_UP + 1u);
+        atomicMax(&slot->n_big, tot);
+        atomicMax(&slot->n_tiles_next, ((tot < 2 || tot > L0W_MAX_BINS) ? 0x80000000u : 0u) | pkd[block].b);
+    }
+}
+
+// LDS of the wide histogram and scatter: bitmap, rank table, bs counters, [the staged positions,] the window
+struct L0wLds
+{
+    uint32_t* bm;
+    uint16_t* rk;
+    uint32_t* cnt;
+    uint16_t* st;
+    uint8_t*  win;
+    __device__ L0wLds(char* p, uint32_t bs, bool staged)
+    {
+        bm  = reinterpret_cast<uint32_t*>(p);
+        rk  = reinterpret_cast<uint16_t*>(p + L0W_BMW * 4);
+        cnt = reinterpret_cast<uint32_t*>(p + L0W_BMW * 6);
+        st  = reinterpret_cast<uint16_t*>(p + L0W_BMW * 6 + bs * 4);
+        win = reinterpret_cast<uint8_t*>(p + L0W_BMW * 6 + bs * 4 + (staged ? L0W_TILE * 2 : 0));  // bs is a multiple of 4: 16-byte aligned
+    }
+};
+static size_t l0w_lds_bytes(uint32_t bs, bool staged, uint32_t bits = 8)  // bits: the widest character of the call
+{
+    return L0W_BMW * 6 + (size_t) bs * 4 + (staged ? L0W_TILE * 2 : 0) + L0W_TILE * bits / 8 + 64;
+}
+
+__device__ __forceinline__ void l0w_load_map(const uint32_t* __restrict__ bm, const uint16_t* __restrict__ rk, uint32_t block, uint32_t bs, L0wLds& S)
+{
+    for (uint32_t i = threadIdx.x; i < L0W_BMW; i += L0W_THREADS)
+    {
+        S.bm[i] = bm[(size_t) block * L0W_BMW + i];
+        S.rk[i] = rk[(size_t) block * L0W_BMW + i];
+    }
+    for (uint32_t i = threadIdx.x; i < bs; i += L0W_THREADS)
+        S.cnt[i] = 0;
+}
+
+// dense 16-bit count row of every tile (a count is at most L0W_TILE < 65536)
+__global__ void __launch_bounds__(L0W_THREADS) k_l0w_hist(const uint8_t* __restrict__ packed, const BlockDesc* __restrict__ blocks,
+                                                          const PackDesc* __restrict__ pkd, const L0Tile* __restrict__ tiles, uint32_t ntiles,
+                                                          const uint32_t* __restrict__ bm, const uint16_t* __restrict__ rk, uint32_t bs,
+                                                          uint16_t* __restrict__ rows)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    L0wLds         S(smem, bs, false);
+    const uint32_t t = blockIdx.x;
+    if (t >= ntiles)
+        return;
+    const L0Tile   T   = tiles[t];
+    const PackDesc P   = pkd[T.block];
+    const uint32_t cnt = min(L0W_TILE, blocks[T.block].len - T.start);
+    l0w_load_window(packed + P.poff, T.start, cnt, P.b, S.win);
+    l0w_load_map(bm, rk, T.block, bs, S);
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < L0W_PT; ++i)
+    {
+        const uint32_t e = threadIdx.x + i * L0W_THREADS;
+        if (e < cnt)
+        {
+            const uint32_t dn = l0w_dense(S.bm, S.rk, (uint32_t) (win_bits64(S.win, e * P.b) >> 48));
+            if (dn < bs)
+                atomicAdd(&S.cnt[dn], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < bs; i += L0W_THREADS)
+        rows[(size_t) t * bs + i] = (uint16_t) S.cnt[i];
+}
+
+// Per block: each dense bin's running count over the block's tiles (off, the tile's offset inside the
+// bin's sub-bucket) and its total.  Workgroup (block, part) takes every L0WCS_PARTS-th 256-bin strip.
+constexpr uint32_t L0WCS_PARTS = 4;
+__global__ void __launch_bounds__(256) k_l0w_colscan(const BlockDesc* __restrict__ blocks, const uint32_t* __restrict__ wt0, uint32_t bs,
+                                                     const uint16_t* __restrict__ rows, uint32_t* __restrict__ off, uint32_t* __restrict__ tot)
+{
+    const uint32_t block = blockIdx.x / L0WCS_PARTS, part = blockIdx.x % L0WCS_PARTS;
+    const uint32_t t0 = wt0[block], nt = div_up(blocks[block].len, L0W_TILE);
+    for (uint32_t i = part * 256 + threadIdx.x; i < bs; i += 256 * L0WCS_PARTS)
+    {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < nt; ++t)
+        {
+            const size_t   at = (size_t) (t0 + t) * bs + i;
+            const uint32_t c  = rows[at];
+            off[at]           = run;
+            run += c;
+        }
+        tot[(size_t) block * bs + i] = run;
+    }
+}
+
+// One depth-1 bucket per (block, first key byte): the bins of one first byte are contiguous in dense order.
+__global__ void __launch_bounds__(256) k_l0w_buckets(const BlockDesc* __restrict__ blocks, const uint32_t* __restrict__ bm,
+                                                     const uint16_t* __restrict__ rk, uint32_t bs, const uint32_t* __restrict__ tot,
+                                                     Bucket* __restrict__ out)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t  block = blockIdx.x, d0 = threadIdx.x, lane = d0 & 63, wv = d0 >> 6;
+    const uint32_t* g     = bm + (size_t) block * L0W_BMW + d0 * 8;
+    uint32_t        nb    = 0;
+    for (int k = 0; k < 8; ++k)
+        nb += __popc(g[k]);
+    const uint32_t lo = rk[(size_t) block * L0W_BMW + d0 * 8];
+    uint32_t       len = 0;
+    for (uint32_t i = lo; i < min(lo + nb, bs); ++i)
+        len += tot[(size_t) block * bs + i];
+    uint32_t x = len;
+    for (int d = 1; d < 64; d <<= 1)
+    {
+        const uint32_t y = __shfl_up(x, d, WAVE);
+        if ((int) lane >= d)
+            x += y;
+    }
+    if (lane == 63)
+        wsum[wv] = x;
+    __syncthreads();
+    uint32_t start = x - len;
+    for (uint32_t k = 0; k < wv; ++k)
+        start += wsum[k];
+    out[(size_t) block * 256 + d0] = Bucket{(uint32_t) blocks[block].off + start, len, 1u, 0u, block, 2u, 0u, 0u};
+}
+
+__global__ void __launch_bounds__(L0W_THREADS) k_l0w_scatter(const uint8_t* __restrict__ in, const uint32_t* __restrict__ amask,
+                                                             const uint8_t* __restrict__ packed, const BlockDesc* __restrict__ blocks,
+                                                             const PackDesc* __restrict__ pkd, const L0Tile* __restrict__ tiles, uint32_t ntiles,
+                                                             const uint32_t* __restrict__ bm, const uint16_t* __restrict__ rk, uint32_t bs,
+                                                             const uint32_t* __restrict__ off, const uint32_t* __restrict__ base,
+                                                             uint64_t* __restrict__ opay, uint8_t* __restrict__ odig, uint32_t* __restrict__ p32)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ uint32_t wsum[L0W_THREADS / 64];
+    __shared__ uint8_t  inv_s[256];
+    __shared__ uint32_t prev_s;
+    L0wLds         S(smem, bs, true);
+    // XCD-major: workgroup w runs on XCD w % 8 and takes a tile of that XCD's contiguous eighth of the
+    // list, so the runs that neighbouring tiles write into one sub-bucket meet in the same L2
+    const uint32_t per = div_up(ntiles, 8u), t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if ((blockIdx.x >> 3) >= per || t >= ntiles)
+        return;
+    const L0Tile    T   = tiles[t];
+    const BlockDesc B   = blocks[T.block];
+    const PackDesc  P   = pkd[T.block];
+    const uint32_t  cnt = min(L0W_TILE, B.len - T.start);
+    l0w_load_window(packed + P.poff, T.start, cnt, P.b, S.win);
+    l0w_load_map(bm, rk, T.block, bs, S);
+    if (threadIdx.x < 256)
+    {
+        // alphabet rank -> byte value (the packing's map, inverted): thread v = byte value v
+        const uint32_t  vv = threadIdx.x;
+        const uint32_t* m  = amask + 8 * T.block;
+        uint32_t        r  = __popc(m[vv >> 5] & ((1u << (vv & 31)) - 1u));
+        for (uint32_t k = 0; k < (vv >> 5); ++k)
+            r += __popc(m[k]);
+        if ((m[vv >> 5] >> (vv & 31)) & 1u)
+            inv_s[r] = (uint8_t) vv;
+        if (threadIdx.x == 0)
+            prev_s = in[B.off + (T.start ? T.start - 1 : B.len - 1)];
+    }
+    __syncthreads();
+    // bin and arrival number inside the bin of each element (the order inside a run is arbitrary: every
+    // consumer of a bucket sorts or splits it on later key bytes)
+    uint32_t keep[L0W_PT];
+#pragma unroll
+    for (uint32_t i = 0; i < L0W_PT; ++i)
+    {
+        const uint32_t e = threadIdx.x + i * L0W_THREADS;
+        keep[i]          = ~0u;
+        if (e < cnt)
+        {
+            const uint32_t dn = l0w_dense(S.bm, S.rk, (uint32_t) (win_bits64(S.win, e * P.b) >> 48));
+            if (dn < bs)
+                keep[i] = (dn << 16) | atomicAdd(&S.cnt[dn], 1u);
+        }
+    }
+    __syncthreads();
+    // exclusive scan of the bin counts, in place: thread j owns bins [j * K, (j + 1) * K)
+    {
+        const uint32_t K = div_up(bs, L0W_THREADS), lo = threadIdx.x * K, hi = min(lo + K, bs), lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        uint32_t       sum = 0;
+        for (uint32_t k = lo; k < hi; ++k)
+            sum += S.cnt[k];
+        uint32_t x = sum;
+        for (int d = 1; d < 64; d <<= 1)
+        {
+            const uint32_t y = __shfl_up(x, d, WAVE);
+            if ((int) lane >= d)
+                x += y;
+        }
+        if (lane == 63)
+            wsum[wv] = x;
+        __syncthreads();
+        uint32_t run = x - sum;
+        for (uint32_t k = 0; k < wv; ++k)
+            run += wsum[k];
+        for (uint32_t k = lo; k < hi; ++k)
+        {
+            const uint32_t c = S.cnt[k];
+            S.cnt[k]         = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < L0W_PT; ++i)
+        if (keep[i] != ~0u)
+            S.st[S.cnt[keep[i] >> 16] + (keep[i] & 0xFFFFu)] = (uint16_t) (threadIdx.x + i * L0W_THREADS);
+    __syncthreads();
+    // bin -> (slot of the tile's run) - (staged position of the run), modulo 2^31, NEXT_FLAG kept in bit 31
+    for (uint32_t i = threadIdx.x; i < bs; i += L0W_THREADS)
+    {
+        const uint32_t g = base[(size_t) T.block * bs + i];
+        S.cnt[i]         = (((g & ~NEXT_FLAG) + off[(size_t) t * bs + i] - S.cnt[i]) & ~NEXT_FLAG) | (g & NEXT_FLAG);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < L0W_PT; ++i)
+    {
+        const uint32_t q = threadIdx.x + i * L0W_THREADS;
+        if (q < cnt)
+        {
+            const uint32_t e    = S.st[q];
+            const uint64_t kk   = win_bits64(S.win, e * P.b);  // key bytes 0..7
+            const uint32_t dn   = l0w_dense(S.bm, S.rk, (uint32_t) (kk >> 48));
+            const uint32_t g    = S.cnt[min(dn, bs - 1)];
+            const uint32_t slot = (g + q) & ~NEXT_FLAG;
+            const uint32_t pos  = T.start + e;
+            // the output byte: the character before the element in the packed window, mapped back from
+            // its alphabet rank (the tile's first element: the byte read ahead)
+            const uint32_t lb = e ? inv_s[(uint32_t) (win_bits64(S.win, (e - 1) * P.b) >> (64 - P.b))] : prev_s;
+            if (slot >= B.off && slot < B.off + B.len)
+            {
+                if (g & NEXT_FLAG)
+                {
+                    opay[slot] = ((kk << 16) & 0xFFFFFFFF00000000ull) | ((uint64_t) lb << 24) | pos;  // key bytes 2..5
+                    odig[slot] = (uint8_t) (kk >> 40);                                                 // key byte 2: the depth-2 digit
+                }
+                else
+                    p32[slot] = (lb << 24) | pos;  // a job's element: the job reads only the low word
+            }
+        }
     }
 }
 
@@ -3428,6 +3829,24 @@ struct BwtWorkspace
     uint32_t* l0base         = nullptr;  // per block: level-0 sub-bucket starts (k_scan)
     std::vector<BlockDesc> geo;          // block geometry the level-0 tiles / buckets on the device were built for
     uint32_t  nt0 = 0;
+    // wide first split (k_l0w_*)
+    L0Tile*   l0wtiles       = nullptr;  // tiles of L0W_TILE positions
+    uint32_t* l0w_t0         = nullptr;  // per block: its first wide tile
+    uint32_t* l0w_bm         = nullptr;  // per block: presence bitmap of the 16-bit prefixes
+    uint16_t* l0w_rk         = nullptr;  // per block: rank table of the bitmap
+    uint32_t* l0w_tot        = nullptr;  // per block: dense bin totals
+    uint32_t* l0w_base       = nullptr;  // per block: dense sub-bucket starts (| NEXT_FLAG)
+    Bucket*   l0wb           = nullptr;  // 256 depth-1 buckets per block
+    uint32_t  ntw            = 0;        // wide tiles of the cached geometry
+    bool      geo_wide       = false;    // every block of the cached geometry has at least one full wide tile
+    uint32_t  cap_wblk       = 0;        // blocks the wide buffers hold
+    uint64_t  cap_th         = 0;        // dwords of tile_hist / tile_off
+    bool      l0_wide        = true;     // BRA_L0_WIDE
+    bool      hist_ahead     = true;     // the last call took the 8-bit level 0: queue its histogram before reading the path
+    uint32_t  last_path      = 0;        // the last encode's path (1: wide) and its largest prefix count
+    uint32_t  last_max_bins  = 0;
+    uint32_t  last_bs        = 0;
+    uint64_t  last_N         = 0;
     uint32_t  cap_tiles = 0, cap_big = 0, cap_jobs = 0, cap_mjobs = 0, cap_groups = 0, cap_l0 = 0;
     int       grid       = 16384;     // workgroups of the MSD / level-0 tile kernels (2048: 11.9, 8192: 12.3, 16384: 12.5 GB/s)
     uint32_t  scan_grid  = 4096;      // workgroups of a level's scan (4 buckets each per pass)
@@ -3581,7 +4000,7 @@ static void ws_free(BwtWorkspace& w)
     }
     void* dev[] = {w.fsa,      w.isa,   w.p32,   w.tile_hist, w.tile_off, w.nomove, w.flag, w.jobs, w.mjobs, w.jobs_sorted, w.mjobs_sorted,
                    w.job_cnt,  w.jseg,  w.tile_cnt,  w.tile_order, w.ctr,  w.jobq,  w.l0tiles, w.l0b, w.packed, w.pkd, w.amask, w.tmask, w.l0tot, w.l0base,
-                   w.audit_cnt};
+                   w.audit_cnt, w.l0wtiles, w.l0w_t0, w.l0w_bm, w.l0w_rk, w.l0w_tot, w.l0w_base, w.l0wb};
     for (void* p : dev)
         (void) hipFree(p);
     if (w.h_ctr)
@@ -3592,12 +4011,25 @@ static void ws_free(BwtWorkspace& w)
     // the old one (the host allocator reuses it) with the old records still in it, and a counter that
     // restarted at 1 would meet their sequence numbers again -- wait_mail then took a stale record
     // for the device's answer (order- and timing-dependent wrong level counts / fallback groups).
-    const uint32_t seq = w.mail_seq;
-    w                  = BwtWorkspace{};
-    w.mail_seq         = seq;
+    const uint32_t seq  = w.mail_seq;
+    const bool     wide = w.l0_wide;
+    w                   = BwtWorkspace{};
+    w.mail_seq          = seq;
+    w.l0_wide           = wide;
 }
 
-BwtWorkspace* bwt_workspace_create() { return new BwtWorkspace(); }
+BwtWorkspace* bwt_workspace_create()
+{
+    BwtWorkspace* w = new BwtWorkspace();
+    const char*   e = getenv("BRA_L0_WIDE");  // 0: always the 8-bit level 0 (A/B runs); read once per context
+    w->l0_wide      = !(e && atoi(e) == 0);
+    return w;
+}
+void bwt_last_path(const BwtWorkspace* w, uint32_t* path, uint32_t* max_bins)
+{
+    *path     = w ? w->last_path : 0;
+    *max_bins = w ? w->last_max_bins : 0;
+}
 const uint32_t* bwt_alpha_masks(const BwtWorkspace* w) { return w ? w->amask : nullptr; }
 const uint32_t* bwt_sa(const BwtWorkspace* w) { return w ? w->fsa : nullptr; }
 void            bwt_forget_jobs(BwtWorkspace* w)
@@ -3647,6 +4079,13 @@ static bool ws_reserve(BwtWorkspace& w, uint64_t n, uint32_t nblocks)
          dev_alloc(w.jobq, (1 + MJ_CLASSES) * 8 * 32) && dev_alloc(w.l0tiles, w.cap_l0) && dev_alloc(w.l0b, B) &&
          dev_alloc(w.packed, N + (uint64_t) PACK_PAD * B + 128) && dev_alloc(w.pkd, B) && dev_alloc(w.amask, 8ull * B) &&
          dev_alloc(w.tmask, 8ull * w.cap_l0) && dev_alloc(w.l0tot, 256ull * B) && dev_alloc(w.l0base, 256ull * B);
+    // wide first split: its blocks have >= L0W_TILE elements each, so at most N / L0W_TILE of them
+    const uint64_t wblk = N / L0W_TILE + 1;
+    ok = ok && dev_alloc(w.l0wtiles, 2 * wblk) && dev_alloc(w.l0w_t0, wblk) && dev_alloc(w.l0w_bm, wblk * (L0W_BMW + 1)) &&
+         dev_alloc(w.l0w_rk, wblk * L0W_BMW) && dev_alloc(w.l0w_tot, wblk * L0W_MAX_BINS) && dev_alloc(w.l0w_base, wblk * L0W_MAX_BINS) &&
+         dev_alloc(w.l0wb, wblk * 256);
+    w.cap_wblk = (uint32_t) wblk;
+    w.cap_th   = (uint64_t) tmax * 256;
     if (ok && hipHostMalloc(&w.h_ctr, MAX_LEVELS * sizeof(Counters), hipHostMallocDefault) != hipSuccess)
         w.h_ctr = nullptr, ok = false;
     if (ok && hipHostMalloc(&w.h_mail, MAX_LEVELS * sizeof(Mail), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
@@ -3728,7 +4167,7 @@ static int level_grid(int dflt)
 
 template <uint32_t MODE>
 static bool run_levels(BwtWorkspace& w, const uint8_t* d_in, const BlockDesc* d_blocks, int cur, Group* groups_out, hipStream_t s,
-                       uint32_t first_seq)
+                       uint32_t first_seq, uint32_t d1 = 1)
 {
     const size_t   lds    = tile_stage_bytes();
     const int      grid   = level_grid(w.grid);
@@ -3739,15 +4178,17 @@ static bool run_levels(BwtWorkspace& w, const uint8_t* d_in, const BlockDesc* d_
     // scatter re-gathers digits (once per CARRY levels) lists its tiles XCD-major and block-major
     // (the gathers then stay in the XCD's L2); the other levels only stream payloads and take the
     // scan's tile-order descriptors as they are (no ordering kernels).
-    uint32_t lvl_kd = 1;
+    // Slot 1 holds buckets of depth d1 (1 after the 8-bit level 0, 2 after the wide first split):
+    // level k works at depth k + d1 - 1.
+    uint32_t lvl_kd = d1;
     uint32_t k = 1, known = 0, nb_known = 1;
     while (true)
     {
         if (known > 0 && nb_known == 0)
             break;  // slot `known` is empty: level `known` and every later one have nothing to do
-        if (k <= max_lv && k <= known + w.lookahead)
+        if (k + d1 - 1 <= max_lv && k <= known + w.lookahead)
         {
-            const uint32_t  lvl_d   = k;
+            const uint32_t  lvl_d   = k + d1 - 1;
             const bool      rg      = lvl_d + 1 - lvl_kd >= CARRY;
             const bool      ordered = rg;
             const Counters* lin     = w.ctr + k;
@@ -3807,7 +4248,7 @@ static bool run_levels(BwtWorkspace& w, const uint8_t* d_in, const BlockDesc* d_
             return false;
         ++known;
         nb_known = m.n_big;
-        if (known > max_lv)
+        if (known + d1 - 1 > max_lv)
             break;
     }
     w.levels = k - 1;
@@ -3826,6 +4267,12 @@ static bool account_levels(BwtWorkspace& w, hipStream_t s)
     // STRING: 8-byte payloads moved (+ the next digit gathered for elements that stay in big buckets);
     // elements leaving for a job write a 4-byte word instead, so this is an upper estimate
     const double eb = 8.0, mb = (MODE == MODE_STRING) ? 16.0 + 8.0 / CARRY : 24.0;
+    if (MODE == MODE_STRING && w.last_path == 1)
+    {
+        // the wide first split's stores: payload + digit byte for the elements of depth-2 buckets, a 4-byte word for the others
+        const double ne = w.h_ctr[1].n_elems_next;
+        prof_bytes(P_BWT_L0SCATTER, 9.0 * ne + 4.0 * ((double) w.last_N - ne));
+    }
     for (uint32_t k = 1; k + 1 < ns; ++k)
     {
         const Counters& c  = w.h_ctr[k];
@@ -3990,6 +4437,8 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
         const size_t lds = tile_stage_bytes();
         BRA_HIP_CHECK(hipFuncSetAttribute((const void*) k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
         BRA_HIP_CHECK(hipFuncSetAttribute((const void*) k_l0_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (sizeof(TileStageL0) + TILE + 64)));
+        BRA_HIP_CHECK(hipFuncSetAttribute((const void*) k_l0w_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int) l0w_lds_bytes(L0W_MAX_BINS, false)));
+        BRA_HIP_CHECK(hipFuncSetAttribute((const void*) k_l0w_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int) l0w_lds_bytes(L0W_MAX_BINS, true)));
         attr_set.fetch_or(dev_bit);
     }
     const int grid = w.grid;
@@ -4007,6 +4456,31 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
                 tiles.push_back(L0Tile{b, st});
         }
         w.geo.clear();
+        // wide tiles, when every block has a full one (and the buffers sized for such blocks hold them)
+        w.geo_wide = nblocks <= w.cap_wblk;
+        for (uint32_t b = 0; b < nblocks && w.geo_wide; ++b)
+            w.geo_wide = h_blocks[b].len >= L0W_TILE;
+        w.ntw = 0;
+        if (w.geo_wide)
+        {
+            std::vector<L0Tile>   wt;
+            std::vector<uint32_t> wt0(nblocks);
+            for (uint32_t b = 0; b < nblocks; ++b)
+            {
+                wt0[b] = (uint32_t) wt.size();
+                for (uint32_t st = 0; st < h_blocks[b].len; st += L0W_TILE)
+                    wt.push_back(L0Tile{b, st});
+            }
+            w.ntw = (uint32_t) wt.size();
+            if (w.ntw > 2 * (uint64_t) w.cap_wblk)
+                w.geo_wide = false;
+            else
+            {
+                BRA_HIP_CHECK(hipMemcpyAsync(w.l0wtiles, wt.data(), w.ntw * sizeof(L0Tile), hipMemcpyHostToDevice, s));
+                BRA_HIP_CHECK(hipMemcpyAsync(w.l0w_t0, wt0.data(), nblocks * 4, hipMemcpyHostToDevice, s));
+                BRA_HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
         w.nt0 = (uint32_t) tiles.size();
         BRA_HIP_CHECK(hipMemcpyAsync(w.l0tiles, tiles.data(), w.nt0 * sizeof(L0Tile), hipMemcpyHostToDevice, s));
         BRA_HIP_CHECK(hipMemcpyAsync(w.l0b, l0b.data(), nblocks * sizeof(Bucket), hipMemcpyHostToDevice, s));
@@ -4025,11 +4499,93 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
         hipLaunchKernelGGL(k_pack, dim3(std::min<uint32_t>(nt0, grid)), dim3(TPB), 0, s, d_in, d_blocks, w.l0tiles, nt0, w.amask, w.pkd, w.packed);
         BRA_DSYNC(s);
     }
-    {
+    auto l0_hist = [&] {
         BRA_PROF(P_BWT_L0HIST, s);
         hipLaunchKernelGGL(k_l0_hist, dim3(std::min<uint32_t>(nt0, grid)), dim3(TPB), 0, s, w.packed, d_blocks, w.pkd, w.l0tiles, nt0, w.tile_hist);
         BRA_DSYNC(s);
+    };
+    // ---- the path of this call: wide first split where every block's 16-bit prefix set is sparse ----
+    // The host reads the answer from the mailbox (no copy, no stream synchronisation).  A context whose
+    // last call took the 8-bit level 0 queues that level's histogram before it waits, so such calls
+    // (uniform random bytes) pay the prefix map and the mailbox read only.
+    bool     wide = false, hist_queued = false;
+    uint32_t maxb = 0, bs = 0, wbits = 8;
+    const uint32_t ntw = w.ntw;
+    if (w.l0_wide && w.geo_wide)
+    {
+        uint32_t seq;
+        {
+            BRA_PROF(P_BWT_L0HIST, s);
+            // (the blocks' "given up" flags sit right behind the bitmaps: one memset)
+            uint32_t* over = w.l0w_bm + (size_t) nblocks * L0W_BMW;
+            BRA_HIP_CHECK(hipMemsetAsync(w.l0w_bm, 0, ((size_t) nblocks * L0W_BMW + nblocks) * 4, s));
+            hipLaunchKernelGGL(k_l0w_bins, dim3(nblocks), dim3(L0W_THREADS), 0, s, w.packed, d_blocks, w.pkd, w.l0wtiles, ntw, w.l0w_t0, 0u, w.l0w_bm, over);
+            BRA_DSYNC(s);
+            if (ntw > nblocks)
+                hipLaunchKernelGGL(k_l0w_bins, dim3(ntw), dim3(L0W_THREADS), 0, s, w.packed, d_blocks, w.pkd, w.l0wtiles, ntw, w.l0w_t0, 1u, w.l0w_bm, over);
+            BRA_DSYNC(s);
+            hipLaunchKernelGGL(k_l0w_rank, dim3(nblocks), dim3(1024), 0, s, w.l0w_bm, over, w.pkd, w.l0w_rk, w.ctr + L0W_SLOT); BRA_DSYNC(s);
+            seq = post(w, L0W_SLOT, s);
+        }
+        if (w.hist_ahead)
+        {
+            l0_hist();
+            hist_queued = true;
+        }
+        Mail m{};
+        if (!wait_mail(w, L0W_SLOT, seq, s, m))
+            return false;
+        maxb = m.n_big;
+        bs   = (maxb + 3u) & ~3u;
+        // the rows of 16-bit counts and of offsets live in tile_hist / tile_off
+        wbits = std::min<uint32_t>(std::max<uint32_t>(m.n_tiles & 0xFFu, 1u), 8u);
+        wide  = !(m.n_tiles >> 31) && (uint64_t) ntw * bs <= w.cap_th;
+        prof_bytes(P_BWT_L0HIST, (double) N + 12288.0 * nblocks);
     }
+    w.hist_ahead    = !wide;
+    w.last_path     = wide ? 1u : 0u;
+    w.last_max_bins = maxb;
+    w.last_bs       = bs;
+    w.last_N        = N;
+    if (wide)
+    {
+        const size_t lds_h = l0w_lds_bytes(bs, false, wbits), lds_s = l0w_lds_bytes(bs, true, wbits);
+        {
+            BRA_PROF(P_BWT_L0HIST, s);
+            hipLaunchKernelGGL(k_l0w_hist, dim3(ntw), dim3(L0W_THREADS), lds_h, s, w.packed, d_blocks, w.pkd, w.l0wtiles, ntw, w.l0w_bm, w.l0w_rk, bs,
+                               reinterpret_cast<uint16_t*>(w.tile_hist));
+            BRA_DSYNC(s);
+        }
+        ScanArgs aw{d_blocks, w.l0wb,    nblocks * 256u,  w.tile_hist, w.tile_off, w.nomove,   w.big[0],    w.cap_big,
+                    w.tile_bucket[0], w.tdesc[0], w.cap_tiles, w.jobs,     w.cap_jobs, w.mjobs,    w.cap_mjobs, w.groups[0],
+                    w.cap_groups,     w.ctr,       DCAP_BIG,   (uint32_t) (g_prof != nullptr), w.mjob_max(), nullptr, w.ctr + 1, w.pkd,
+                    w.l0w_tot,        w.l0w_base,  w.l0w_bm,   w.l0w_rk,   bs};
+        {
+            BRA_PROF(P_BWT_SCAN, s);
+            hipLaunchKernelGGL(k_l0w_colscan, dim3(nblocks * L0WCS_PARTS), dim3(256), 0, s, d_blocks, w.l0w_t0, bs,
+                               reinterpret_cast<const uint16_t*>(w.tile_hist), w.tile_off, w.l0w_tot);
+            BRA_DSYNC(s);
+            hipLaunchKernelGGL(k_l0w_buckets, dim3(nblocks), dim3(256), 0, s, d_blocks, w.l0w_bm, w.l0w_rk, bs, w.l0w_tot, w.l0wb); BRA_DSYNC(s);
+            hipLaunchKernelGGL(k_scan<MODE_STRING>, dim3(std::min<uint32_t>(div_up(nblocks * 256u, SCAN_WAVES), 65535u)), dim3(64 * SCAN_WAVES), 0, s, aw);
+            BRA_DSYNC(s);
+        }
+        {
+            BRA_PROF(P_BWT_L0SCATTER, s);
+            hipLaunchKernelGGL(k_l0w_scatter, dim3(round8(ntw)), dim3(L0W_THREADS), lds_s, s, d_in, w.amask, w.packed, d_blocks, w.pkd, w.l0wtiles, ntw,
+                               w.l0w_bm, w.l0w_rk, bs, w.tile_off, w.l0w_base, w.key[0], w.dig[0], w.p32);
+            BRA_DSYNC(s);
+        }
+        BRA_HIP_CHECK(hipGetLastError());
+        const double cells = (double) ntw * bs;
+        prof_bytes(P_BWT_PACK, 3.0 * (double) N);
+        prof_bytes(P_BWT_L0HIST, (double) N + 2.0 * cells + 12288.0 * ntw);         // window in, 16-bit rows out, the prefix map per tile
+        prof_bytes(P_BWT_SCAN, 6.0 * cells + 12.0 * (double) nblocks * bs);          // rows in, offsets out; totals and starts
+        prof_bytes(P_BWT_L0SCATTER, (double) N + 4.0 * cells + 12288.0 * ntw);      // window, offsets, the prefix map; the stores: account_levels
+    }
+    else
+    {
+    if (!hist_queued)
+        l0_hist();
     ScanArgs a0{d_blocks, w.l0b,     nblocks,         w.tile_hist, w.tile_off, w.nomove,   w.big[0],    w.cap_big,
                 w.tile_bucket[0], w.tdesc[0], w.cap_tiles, w.jobs,     w.cap_jobs, w.mjobs,    w.cap_mjobs, w.groups[0],
                 w.cap_groups,     w.ctr,       DCAP_BIG,   (uint32_t) (g_prof != nullptr), w.mjob_max(), nullptr, w.ctr + 1, w.pkd,
@@ -4051,6 +4607,7 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
     prof_bytes(P_BWT_L0HIST, (double) N + 1024.0 * nt0);
     prof_bytes(P_BWT_SCAN, 3072.0 * nt0);
     prof_bytes(P_BWT_L0SCATTER, 9.0 * N + 1024.0 * nt0);  // window in, payload out
+    }
     // level-0 sub-buckets all live in KV buffer 0, their tiles in tile_bucket[0]; the jobs run after
     // the last level
     JobPhase ph;
@@ -4060,7 +4617,7 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
     ph.jm      = ph.ja;
     ph.jm.jobs = w.mjobs;
     ph.nblocks = nblocks;
-    if (!run_levels<MODE_STRING>(w, d_in, d_blocks, 0, w.groups[0], s, post(w, 1, s)))
+    if (!run_levels<MODE_STRING>(w, d_in, d_blocks, 0, w.groups[0], s, post(w, 1, s), wide ? 2u : 1u))
         return false;
     if (!run_jobs(w, ph, s))
         return false;
@@ -4087,6 +4644,8 @@ bool bwt_encode_enqueue(BwtWorkspace* wp, const uint8_t* d_in, const BlockDesc* 
         const Counters& c0 = w.h_ctr[0];
         fprintf(stderr, "[bwt levels] N %llu jobs %u mjobs %u melems %u groups %u\n", (unsigned long long) N, c0.n_jobs,
                 c0.n_mjobs, c0.n_melems, c0.n_groups);
+        fprintf(stderr, "[bwt levels] first split: %s (max 16-bit prefixes per block %u), slot 1 holds depth-%u buckets\n",
+                wide ? "wide" : "8-bit", maxb, wide ? 2u : 1u);
         for (uint32_t k = 1; k < ns; ++k)
             fprintf(stderr, "[bwt levels] slot %u: buckets %u tiles %u elems %u moved(into) %u\n", k, w.h_ctr[k].n_big, w.h_ctr[k].n_tiles_next,
                     w.h_ctr[k].n_elems_next, w.h_ctr[k].n_moved);

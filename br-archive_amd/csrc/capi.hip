@@ -1,6 +1,7 @@
 // capi.hip -- the C-ABI of libbra_hip.so (include/bra_hip.h): the reference's 14 encoder entry
 // points (single block, host buffers) and the batched device-resident codec.
 #include "../../include/bra_hip.h"
+#include "../../include/bra_hip_debug.h"
 
 #include "bwt.h"
 #include "crc.h"
@@ -1248,6 +1249,20 @@ int bra_gpu_debug_rerun_jobs(bra_gpu_ctx_t* c, int reps, unsigned shuffle_seed)
         return -1;
     DevGuard dg(c->device);
     return bwt_debug_rerun_jobs(c->bwt, reps, c->stream, shuffle_seed);
+}
+
+// Diagnostics: the first BWT split the last batch encode on the context took (1: wide, placing
+// rotations by their first two packed key bytes; 0: the 8-bit level 0) and the largest number of
+// distinct 16-bit packed prefixes in one of its blocks (0 when the call never built the prefix maps).
+int bra_gpu_debug_bwt_path(bra_gpu_ctx_t* c, unsigned* path, unsigned* max_bins)
+{
+    if (!c || !path || !max_bins)
+        return -1;
+    uint32_t p = 0, b = 0;
+    bwt_last_path(c->bwt, &p, &b);
+    *path     = p;
+    *max_bins = b;
+    return 0;
 }
 
 const char* bra_gpu_version(void) { return "bra_hip 0.1.0 (gfx950)"; }

@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "bra_gpu_debug_rerun_jobs", "bra_gpu_sortnet_selftest",
     "bra_gpu_host_alloc", "bra_gpu_host_free", "bra_gpu_compress_chunks_stage", "bra_gpu_compress_chunks_submit", "bra_gpu_compress_chunks_collect",
 )
+# Exported symbols of include/bra_hip_files.h (Part 5: many files in one call; tests/test_files_abi.py).
+FILES_ABI_SYMBOLS = ("bra_gpu_files_bound", "bra_gpu_compress_files", "bra_gpu_decompress_files")
 MAX_CHUNK_SIZE = 256 * 1024  # BRA_MAX_CHUNK_SIZE (src/lib_bra_defs.h:93): the .BRa chunk size
 
 SYNTH_TEXT, SYNTH_RANDOM, SYNTH_SYM16, SYNTH_TILED = 0, 1, 2, 3
@@ -64,6 +66,18 @@ class _HuffmanChunk(C.Structure):
 
 
 assert C.sizeof(HuffmanMeta) == 264 and _HuffmanChunk.data.offset == 264
+
+
+class FileResult(C.Structure):
+    """bra_gpu_file_result_t (include/bra_hip_files.h): one per file of a compress_files /
+    decompress_files call."""
+
+    _fields_ = [("off", C.c_uint64), ("size", C.c_uint64), ("chunks_crc", C.c_uint32), ("raw_crc", C.c_uint32),
+                ("num_chunks", C.c_uint32), ("compressed", C.c_uint32)]
+
+
+assert C.sizeof(FileResult) == 32
+FILE_RESULT_FIELDS = [("off", "<u8"), ("size", "<u8"), ("chunks_crc", "<u4"), ("raw_crc", "<u4"), ("num_chunks", "<u4"), ("compressed", "<u4")]
 
 
 @dataclass
@@ -168,6 +182,12 @@ def _load() -> C.CDLL:
     lib.bra_gpu_assemble_shards.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u32p, C.c_int, vp, vp, vp,
                                             C.c_uint64, vp]
     lib.bra_gpu_assemble_shards.restype = C.c_int
+    lib.bra_gpu_files_bound.argtypes = [u64p, C.c_uint32, C.c_uint32]
+    lib.bra_gpu_files_bound.restype = C.c_uint64
+    lib.bra_gpu_compress_files.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp]
+    lib.bra_gpu_compress_files.restype = C.c_int
+    lib.bra_gpu_decompress_files.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, u32p, vp]
+    lib.bra_gpu_decompress_files.restype = C.c_int
     return lib
 
 
@@ -494,6 +514,81 @@ class BlockCodec:
         if rc != 0:
             raise ValueError(f"bra_gpu_decompress_chunks rejected the stream ({rc})")
         return out[: osz.value], crc.value
+
+    # ---- many files in one call (include/bra_hip_files.h) ----
+    @staticmethod
+    def files_bound(lengths, block_size: int = MAX_CHUNK_SIZE) -> int:
+        """Output capacity that compress_files of files of these lengths never exceeds (host only)."""
+        n = len(lengths)
+        return lib.bra_gpu_files_bound((C.c_uint64 * max(1, n))(*[int(x) for x in lengths]), n, block_size)
+
+    @staticmethod
+    def _results_numpy(res_t):
+        import numpy as np
+
+        return res_t.cpu().numpy().view(np.dtype(FILE_RESULT_FIELDS))
+
+    def compress_files_raw(self, data, offsets, lengths, block_size: int, out, results=None, out_cap: int | None = None, stream=None):
+        """bra_gpu_compress_files as it is: (return code, *out_size, results as a uint8 CUDA tensor
+        of 32 bytes per file)."""
+        import torch
+
+        n = len(offsets)
+        if results is None:
+            results = torch.empty((max(n, 1) * 32,), dtype=torch.uint8, device=data.device)
+        arr = C.c_uint64 * max(1, n)
+        size = C.c_uint64()
+        rc = lib.bra_gpu_compress_files(self.ctx, data.data_ptr(), arr(*[int(x) for x in offsets]), arr(*[int(x) for x in lengths]), n, block_size,
+                                        out.data_ptr(), out.numel() if out_cap is None else out_cap, C.byref(size), results.data_ptr(),
+                                        _stream_handle(stream))
+        return rc, size.value, results
+
+    def compress_files(self, data, offsets, lengths, block_size: int = MAX_CHUNK_SIZE, out=None, stream=None):
+        """The compress loop over many files in one device call.  File f is data[offsets[f] :
+        offsets[f] + lengths[f]] (ascending, not overlapping).  Returns (the files' chunk streams back
+        to back as a uint8 CUDA tensor, results): results is a NumPy structured array with the
+        fields off, size, chunks_crc, raw_crc, num_chunks, compressed, one row per file."""
+        import torch
+
+        cap = self.files_bound(lengths, block_size)
+        if out is None or out.numel() < cap:
+            out = torch.empty((max(cap, 1),), dtype=torch.uint8, device=data.device)
+        rc, size, res = self.compress_files_raw(data, offsets, lengths, block_size, out, stream=stream)
+        if rc != 0:
+            raise RuntimeError(f"bra_gpu_compress_files failed ({rc})")
+        return out[:size], self._results_numpy(res)
+
+    def decompress_files_raw(self, streams, offsets, sizes, block_size: int, out, results=None, out_cap: int | None = None, stream=None):
+        """bra_gpu_decompress_files as it is: (return code, *out_size, results tensor, *bad_file)."""
+        import torch
+
+        n = len(offsets)
+        if results is None:
+            results = torch.empty((max(n, 1) * 32,), dtype=torch.uint8, device=streams.device)
+        arr = C.c_uint64 * max(1, n)
+        size, bad = C.c_uint64(), C.c_uint32()
+        rc = lib.bra_gpu_decompress_files(self.ctx, streams.data_ptr(), arr(*[int(x) for x in offsets]), arr(*[int(x) for x in sizes]), n, block_size,
+                                          out.data_ptr(), out.numel() if out_cap is None else out_cap, C.byref(size), results.data_ptr(),
+                                          C.byref(bad), _stream_handle(stream))
+        return rc, size.value, results, bad.value
+
+    def decompress_files(self, streams, offsets, sizes, block_size: int = MAX_CHUNK_SIZE, out_cap: int | None = None, stream=None):
+        """The decode loop over many chunk streams in one device call: stream f is streams[offsets[f] :
+        offsets[f] + sizes[f]].  Returns (the decoded files back to back, results as in
+        compress_files).  Raises ValueError, with the lowest rejected file index in `.bad_file`,
+        when a stream is rejected; out_cap None sizes the output from a first call's answer."""
+        import torch
+
+        out = torch.empty((max(out_cap or 1, 1),), dtype=torch.uint8, device=streams.device)
+        rc, size, res, bad = self.decompress_files_raw(streams, offsets, sizes, block_size, out, out_cap=out_cap or 0, stream=stream)
+        if rc == -2 and out_cap is None:
+            out = torch.empty((size,), dtype=torch.uint8, device=streams.device)
+            rc, size, res, bad = self.decompress_files_raw(streams, offsets, sizes, block_size, out, results=res, stream=stream)
+        if rc != 0:
+            e = ValueError(f"bra_gpu_decompress_files rejected the batch ({rc}, bad_file {bad})")
+            e.bad_file = bad if bad != 0xFFFFFFFF else None
+            raise e
+        return out[:size], self._results_numpy(res)
 
     # ---- sharded streams (row e) ----
     def chunks_crc32c_shard(self, data, headers, block_size: int, first_chunk: int, chunk_stride: int, global_total: int,

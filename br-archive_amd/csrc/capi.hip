@@ -34,6 +34,9 @@ void bra_hip_report(const char* fmt, ...)
 static_assert(sizeof(bra_io_chunk_header_t) == 268, "in-memory chunk header layout (lib_bra_types.h:63-68)");
 static_assert(sizeof(bra_huffman_t) == 264, "bra_huffman_t layout");
 static_assert(offsetof(bra_huffman_chunk_t, data) == 264, "bra_huffman_chunk_t layout");
+static_assert(sizeof(bra_gpu_file_result_t) == 32 && sizeof(bra::FileResult) == 32 && offsetof(bra_gpu_file_result_t, chunks_crc) == 16 &&
+                  offsetof(bra::FileResult, chunks_crc) == 16 && offsetof(bra_gpu_file_result_t, compressed) == 28,
+              "bra_gpu_file_result_t layout (files_plan.h FileResult)");
 
 using namespace bra;
 
@@ -219,6 +222,12 @@ struct bra_gpu_ctx_s
     uint64_t       cap_hin = 0, cap_hout = 0;
     uint64_t*      d_enc_rle_base = nullptr;
     uint64_t       cap_eb = 0, cap_erb = 0;
+    // many files in one call: chunk table, long-chunk pieces, stream extents, record counts / firsts
+    FileChunk*     d_frow = nullptr;
+    FilePiece*     d_fpiece = nullptr;
+    uint64_t*      d_fext = nullptr;
+    uint32_t*      d_fcnt = nullptr;
+    uint64_t       cap_frow = 0, cap_fpiece = 0, cap_fext = 0, cap_fcnt = 0;
     hipEvent_t     null_ev = nullptr;  // CallStream: the null stream's position at a NULL-stream call
     hipEvent_t     caller_ev = nullptr;  // CallStream: the end of the last call on a caller-supplied stream
     bool           caller_pending = false;
@@ -265,7 +274,8 @@ static void ctx_free(bra_gpu_ctx_s* c)
     c->hist_tiling.release();
     void* ptrs[] = {c->d_L,       c->d_mtf,   c->d_rle,  c->d_tmp,  c->d_blocks, c->d_pi,  c->d_rle_size, c->d_hist, c->d_status, c->d_rle_base,
                     c->d_rle_cap, c->d_aux,   c->d_meta, c->d_io,     c->d_off, c->d_pay,      c->d_hdr,
-                    c->d_word,    c->d_enc_blocks, c->d_enc_rle_base, c->d_hin, c->d_hout};
+                    c->d_word,    c->d_enc_blocks, c->d_enc_rle_base, c->d_hin, c->d_hout,
+                    c->d_frow,    c->d_fpiece, c->d_fext, c->d_fcnt};
     for (void* p : ptrs)
         (void) hipFree(p);
     for (auto& ps : c->pipe)
@@ -927,6 +937,305 @@ static int decompress_chunks_impl(bra_gpu_ctx_t* c, const uint8_t* d_stream, uin
         *crc_out = crc;
     }
     return cs_.finish(0);
+}
+
+// ---- Part 5: many files in one call (include/bra_hip_files.h; planning in files_plan.h) ----
+
+uint64_t bra_gpu_files_bound(const uint64_t* file_len, uint32_t nfiles, uint32_t block_size) { return files_bound(file_len, nfiles, block_size); }
+
+// The chunk table and the long chunks' piece list on the device (the host vectors must outlive the
+// copies: the callers synchronise the stream before they return).
+static bool upload_chunk_table(bra_gpu_ctx_s* c, const std::vector<FileChunk>& rows, const std::vector<FilePiece>& pieces, hipStream_t s)
+{
+    if (!grow(c->d_frow, c->cap_frow, rows.size()) || !grow(c->d_fpiece, c->cap_fpiece, pieces.size() + 1))
+        return false;
+    BRA_HIP_CHECK(hipMemcpyAsync(c->d_frow, rows.data(), rows.size() * sizeof(FileChunk), hipMemcpyHostToDevice, s));
+    if (!pieces.empty())
+        BRA_HIP_CHECK(hipMemcpyAsync(c->d_fpiece, pieces.data(), pieces.size() * sizeof(FilePiece), hipMemcpyHostToDevice, s));
+    return true;
+}
+
+int bra_gpu_compress_files(bra_gpu_ctx_t* c, const uint8_t* d_in, const uint64_t* file_off, const uint64_t* file_len, uint32_t nfiles,
+                           uint32_t block_size, uint8_t* d_out, uint64_t out_cap, uint64_t* out_size, bra_gpu_file_result_t* d_results,
+                           void* stream)
+{
+    FilesPlan plan;
+    if (!c || !d_results || !files_plan_build(file_off, file_len, nfiles, block_size, plan))
+        return -1;
+    const uint32_t nb = (uint32_t) plan.chunks.size();
+    if (nb && (!d_in || !d_out))
+        return -1;
+    DevGuard dg(c->device);
+    if (!dg.ok)
+        return -1;
+    CallStream cs_(c, stream);
+    hipStream_t s = cs_;
+    // the table as the device kernels find it: the file's length in `size`, its first chunk in
+    // `compressed` (file_table_device), both CRC words at their initial values (crc_files_device)
+    std::vector<FileResult> res(nfiles);
+    for (uint32_t f = 0; f < nfiles; ++f)
+    {
+        const uint32_t n = plan.first[f + 1] - plan.first[f];
+        res[f] = FileResult{0, file_len[f], crc_files_init(file_len[f] + (uint64_t) CHUNK_HDR_MEM * n), crc_files_init(file_len[f]), n, plan.first[f]};
+    }
+    FileResult* d_res = reinterpret_cast<FileResult*>(d_results);
+    std::vector<BlockDesc> hb(nb);
+    for (uint32_t b = 0; b < nb; ++b)
+        hb[b] = BlockDesc{plan.chunks[b].off, plan.chunks[b].len, 0};
+    std::vector<FilePiece> pieces;
+    files_plan_pieces(plan.chunks, pieces);
+    const uint64_t pb = files_payload_bound(file_len, nfiles, block_size);
+    if (!grow(c->d_hdr, c->cap_hdr, nb + 1) || !grow(c->d_off, c->cap_off, nb + 1) || !grow(c->d_pay, c->cap_pay, pb) ||
+        !grow(c->d_word, c->cap_word, 16))
+        return -1;
+    uint64_t* d_total = reinterpret_cast<uint64_t*>(c->d_word + 6);
+    uint64_t  total   = 0;
+    int       rc      = hipMemcpyAsync(d_res, res.data(), (size_t) nfiles * sizeof(FileResult), hipMemcpyHostToDevice, s) == hipSuccess ? 0 : -1;
+    if (nb && rc == 0)
+    {
+        const uint8_t* in = d_in + plan.base;
+        if (!upload_chunk_table(c, plan.chunks, pieces, s))
+        {
+            (void) hipStreamSynchronize(s);
+            return -1;
+        }
+        g_prof = c->prof.mask ? &c->prof : nullptr;
+        rc     = encode_impl(c, in, hb, c->d_hdr, c->d_off, c->d_pay, c->cap_pay, s, nullptr);
+        if (rc == 0 && (!file_table_device(c->d_off, nb, d_res, nfiles, d_total, s) ||
+                        hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
+            rc = -1;
+        if (rc == 0)
+        {
+            if (out_size)
+                *out_size = total;
+            if (total > out_cap)
+                rc = -2;
+        }
+        if (rc == 0)
+        {
+            bool ok;
+            {
+                BRA_PROF(P_FRAME, s);
+                ok = frame_chunks_device(reinterpret_cast<const uint8_t*>(c->d_hdr), c->d_off, c->d_pay, nb, d_out, s);
+            }
+            if (ok)
+            {
+                BRA_PROF(P_CRC, s);
+                ok = crc_files_device(in, reinterpret_cast<const uint8_t*>(c->d_hdr), c->d_frow, nb, c->d_fpiece, (uint32_t) pieces.size(), d_res, s);
+            }
+            if (g_prof)
+            {
+                prof_bytes(P_FRAME, 2.0 * (double) total);
+                prof_bytes(P_CRC, (double) plan.extent + 268.0 * nb);
+            }
+            if (!ok)
+                rc = -1;
+        }
+        g_prof = nullptr;
+    }
+    else if (rc == 0 && out_size)
+        *out_size = 0;  // only empty files: the table as uploaded is the result (first chunk 0 = compressed 0)
+    // the host vectors above are the sources of this call's copies
+    if (hipStreamSynchronize(s) != hipSuccess && rc == 0)
+        rc = -1;
+    return cs_.finish(rc);
+}
+
+// The decode of a batch of chunk streams; *bad_file: the lowest rejected file.
+static int decompress_files_impl(bra_gpu_ctx_s* c, const uint8_t* d_streams, const uint64_t* stream_off, const uint64_t* stream_size,
+                                 uint32_t nfiles, uint32_t block_size, uint8_t* d_out, uint64_t out_cap, uint64_t* out_size,
+                                 FileResult* d_res, uint32_t* bad_file, hipStream_t s)
+{
+    bwt_forget_jobs(c->bwt);
+    uint64_t max_recs = 0;
+    for (uint32_t f = 0; f < nfiles; ++f)
+    {
+        if (stream_off[f] + stream_size[f] < stream_off[f])
+            return -1;
+        max_recs += stream_size[f] / (CHUNK_HDR_DISK + 1);
+    }
+    if (max_recs >= (1u << 26))
+        return -1;
+    const uint32_t cap = (uint32_t) max_recs;
+    std::vector<uint64_t> ext(2ull * nfiles);
+    for (uint32_t f = 0; f < nfiles; ++f)
+    {
+        ext[f]          = stream_off[f];
+        ext[nfiles + f] = stream_size[f];
+    }
+    if (!grow(c->d_fext, c->cap_fext, 2ull * nfiles) || !grow(c->d_fcnt, c->cap_fcnt, 2ull * nfiles) || !grow(c->d_hdr, c->cap_hdr, cap + 1) ||
+        !grow(c->d_off, c->cap_off, cap + 1) || !grow(c->d_word, c->cap_word, 16))
+        return -1;
+    uint32_t* d_status = c->d_word + 8;  // {records, header flag, lowest file rejected by the walk}
+    uint32_t  wst[3]   = {0, 0, 0};
+    std::vector<uint32_t> cnt(nfiles);
+    if (hipMemcpyAsync(c->d_fext, ext.data(), ext.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        !unframe_files_device(d_streams, c->d_fext, c->d_fext + nfiles, nfiles, cap, BRA_MAX_CHUNK, reinterpret_cast<uint8_t*>(c->d_hdr), c->d_off,
+                              c->d_fcnt, c->d_fcnt + nfiles, d_status, s) ||
+        hipMemcpyAsync(cnt.data(), c->d_fcnt, (size_t) nfiles * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(wst, d_status, 12, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return -1;
+    const uint32_t nb = wst[0];
+    if (nb > cap)
+        return -1;
+    // chunks in file order; a file whose walk failed keeps its records before the bad one, so that a
+    // lower file rejected by a later check is still the one reported
+    std::vector<uint32_t> first(nfiles + 1), fbad(nfiles, 0);
+    std::vector<uint32_t> file_of(nb);
+    {
+        uint32_t b = 0;
+        for (uint32_t f = 0; f < nfiles; ++f)
+        {
+            first[f] = b;
+            fbad[f]  = (cnt[f] >> 31) || (cnt[f] & 0x7FFFFFFFu) == 0;
+            for (uint32_t k = 0; k < (cnt[f] & 0x7FFFFFFFu) && b < nb; ++k)
+                file_of[b++] = f;
+        }
+        first[nfiles] = b;
+        if (b != nb)
+            return -1;
+    }
+    std::vector<bra_io_chunk_header_t> hh(nb);
+    std::vector<uint32_t>              st(nb), dsz(nb), rsz(nb), esz(nb);
+    std::vector<uint64_t>              rbase(nb), zeros(nb, 0);
+    if (nb)
+    {
+        if (!ensure_block_arrays(c, nb) ||
+            hipMemcpyAsync(hh.data(), c->d_hdr, (size_t) nb * sizeof(bra_io_chunk_header_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return -1;
+        uint64_t R = 0;
+        for (uint32_t b = 0; b < nb; ++b)
+        {
+            rbase[b] = R;
+            rsz[b]   = hh[b].huffman.orig_size;
+            esz[b]   = hh[b].huffman.encoded_size;
+            R += (uint64_t) rsz[b] + 16;
+        }
+        if (!grow(c->d_rle, c->cap_rle, R + 16) || !grow(c->d_mtf, c->cap_mtf, 16))
+            return -1;
+        // pass 1: Huffman decode, then the RLE decode into a zero capacity: only the decoded sizes
+        uint64_t* d_rbase  = c->d_rle_base;
+        uint64_t* d_outcap = c->d_rle_cap;
+        uint64_t* d_outb   = c->d_aux + nb + 1;
+        uint32_t* d_dec_size = c->d_hist;
+        if (hipMemcpyAsync(d_rbase, rbase.data(), (size_t) nb * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_outcap, zeros.data(), (size_t) nb * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_outb, zeros.data(), (size_t) nb * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(c->d_rle_size, rsz.data(), (size_t) nb * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+            return -1;
+        hipLaunchKernelGGL(k_split_headers, dim3(std::min<uint32_t>(nb, 65535)), dim3(256), 0, s, c->d_hdr, nb, c->d_pi, c->d_meta);
+        {
+            BRA_PROF(P_DEC_HUF, s);
+            if (!huff_decode_device(c->huf, c->d_meta, esz.data(), nb, d_streams, c->d_off, c->d_rle, d_rbase, c->d_status, s))
+                return -1;
+        }
+        if (!rle_decode_device(c->rle, rsz.data(), c->d_rle, d_rbase, c->d_rle_size, nb, c->d_mtf, d_outb, d_outcap, d_dec_size, s))
+            return -1;
+        if (hipMemcpyAsync(st.data(), c->d_status, (size_t) nb * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(dsz.data(), d_dec_size, (size_t) nb * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return -1;
+    }
+    // per-file verdicts (lib_bra_io_file_chunks.c:340-427) and the exact layout
+    std::vector<FileResult> res(nfiles);
+    std::vector<BlockDesc>  g(nb);
+    std::vector<uint64_t>   outb(nb), outcap(nb);
+    uint64_t                total = 0;
+    uint32_t                bad   = 0xFFFFFFFFu;
+    for (uint32_t f = 0; f < nfiles; ++f)
+    {
+        const uint64_t o0 = total;
+        bool           ok = !fbad[f];
+        for (uint32_t b = first[f]; b < first[f + 1]; ++b)
+        {
+            ok        = ok && st[b] == 0 && dsz[b] != 0 && dsz[b] <= block_size && hh[b].primary_index < dsz[b];
+            g[b]      = BlockDesc{total, dsz[b], 0};
+            outb[b]   = total;
+            outcap[b] = dsz[b];
+            total += dsz[b];
+        }
+        const uint32_t n = first[f + 1] - first[f];
+        ok               = ok && total - o0 > stream_size[f];  // the reference's safety check (:423-427)
+        if (!ok && bad == 0xFFFFFFFFu)
+            bad = f;
+        res[f] = FileResult{o0, total - o0, crc_files_init(total - o0 + (uint64_t) CHUNK_HDR_MEM * n), crc_files_init(total - o0), n, 1};
+    }
+    if (bad != 0xFFFFFFFFu)
+    {
+        if (bad_file)
+            *bad_file = bad;
+        bra_hip_report("corrupted file entry: chunk stream of file %u rejected", bad);
+        return -1;
+    }
+    if (out_size)
+        *out_size = total;
+    if (total >= (1ull << 31))
+    {
+        bra_hip_report("decoded batch too large (%llu bytes)", (unsigned long long) total);
+        return -1;
+    }
+    if (total > out_cap)
+    {
+        bra_hip_report("decoded files need %llu bytes, output holds %llu", (unsigned long long) total, (unsigned long long) out_cap);
+        return -2;
+    }
+    // pass 2: the RLE decode again, now to the exact layout, then MTF and the inverse BWT straight
+    // into d_out (the chunks of all files are back to back there)
+    if (!grow(c->d_L, c->cap_L, total + 16) || !grow(c->d_mtf, c->cap_mtf, total + 16) || !grow(c->d_tmp, c->cap_tmp, total + 16))
+        return -1;
+    FilesPlan plan;
+    plan.first = first;
+    plan.chunks.resize(nb);
+    for (uint32_t b = 0; b < nb; ++b)
+        plan.chunks[b] = FileChunk{g[b].off, g[b].len, file_of[b], 0, 0};
+    files_plan_tails(plan);
+    std::vector<FilePiece> pieces;
+    files_plan_pieces(plan.chunks, pieces);
+    if (hipMemcpyAsync(c->d_blocks, g.data(), (size_t) nb * sizeof(BlockDesc), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(c->d_rle_cap, outcap.data(), (size_t) nb * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(c->d_aux + nb + 1, outb.data(), (size_t) nb * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_res, res.data(), (size_t) nfiles * sizeof(FileResult), hipMemcpyHostToDevice, s) != hipSuccess ||
+        !upload_chunk_table(c, plan.chunks, pieces, s))
+        return -1;
+    {
+        BRA_PROF(P_DEC_RLE, s);
+        if (!rle_decode_device(c->rle, rsz.data(), c->d_rle, c->d_rle_base, c->d_rle_size, nb, c->d_mtf, c->d_aux + nb + 1, c->d_rle_cap, c->d_hist, s))
+            return -1;
+    }
+    {
+        BRA_PROF(P_DEC_MTF, s);
+        if (!mtf_decode_device(c->mtf, c->d_mtf, c->d_L, c->d_tmp, g.data(), nb, s))
+            return -1;
+    }
+    {
+        BRA_PROF(P_DEC_IBWT, s);
+        if (!ibwt_device(c->ib, c->d_L, c->d_pi, c->d_blocks, g.data(), nb, d_out, s))
+            return -1;
+    }
+    if (!crc_files_device(d_out, reinterpret_cast<const uint8_t*>(c->d_hdr), c->d_frow, nb, c->d_fpiece, (uint32_t) pieces.size(), d_res, s))
+        return -1;
+    // the host vectors above are the sources of this call's copies
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
+}
+
+int bra_gpu_decompress_files(bra_gpu_ctx_t* c, const uint8_t* d_streams, const uint64_t* stream_off, const uint64_t* stream_size, uint32_t nfiles,
+                             uint32_t block_size, uint8_t* d_out, uint64_t out_cap, uint64_t* out_size, bra_gpu_file_result_t* d_results,
+                             uint32_t* bad_file, void* stream)
+{
+    if (bad_file)
+        *bad_file = 0xFFFFFFFFu;
+    if (!c || !d_streams || !stream_off || !stream_size || nfiles == 0 || !block_size || block_size >= (1u << 24) || !d_out || !d_results)
+        return -1;
+    DevGuard dg(c->device);
+    if (!dg.ok)
+        return -1;
+    CallStream cs_(c, stream);
+    hipStream_t s = cs_;
+    g_prof        = c->prof.mask ? &c->prof : nullptr;
+    const int rc  = decompress_files_impl(c, d_streams, stream_off, stream_size, nfiles, block_size, d_out, out_cap, out_size,
+                                          reinterpret_cast<FileResult*>(d_results), bad_file, s);
+    g_prof        = nullptr;
+    return cs_.finish(rc);
 }
 
 // ---- host-buffer forms for the C front end (row f1; frontend/bra_io_file_chunks_gpu.c) ----

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "bra_hip_common.h"
+#include "files_plan.h"
 
 namespace bra {
 
@@ -43,6 +44,36 @@ bool frame_chunks_device(const uint8_t* d_hdr, const uint64_t* d_payload_off, co
 // d_status receives {number of records, error flag}; cap is the capacity of d_hdr / d_payload_off.
 bool unframe_chunks_device(const uint8_t* d_stream, uint64_t size, uint32_t cap, uint32_t max_chunk, uint8_t* d_hdr, uint64_t* d_payload_off,
                            uint32_t* d_status, hipStream_t s);
+
+// ---- many files in one call (files_plan.h) --------------------------------------------------------
+
+// Both CRC32C values of every file in one pass over the data: chunk b of the table d_rows is
+// d_data[rows[b].off, +len) with its header at d_hdr + 268 * b; its contributions are XORed into
+// d_results[rows[b].file].chunks_crc (header and data, moved by tail_stream) and .raw_crc (data,
+// moved by tail_raw).  The caller has initialised both words of every file to ~((~0) * x^(8 V))
+// with V the length of the respective stream (crc_files_init).  d_pieces: files_plan_pieces of the
+// table.
+bool crc_files_device(const uint8_t* d_data, const uint8_t* d_hdr, const FileChunk* d_rows, uint32_t nrows, const FilePiece* d_pieces,
+                      uint32_t npieces, FileResult* d_results, hipStream_t s);
+// The initial value of a CRC word chained from 0 over a stream of V bytes (0 for V == 0).
+uint32_t crc_files_init(uint64_t V);
+
+// Compress side: d_results[f] holds on entry size = the file's length, num_chunks and, in
+// `compressed`, the file's first chunk index; on exit off / size = the file's chunk stream in the
+// framed output (record b starts at payload_off[b] + 267 * b) and compressed = size < length.
+// *d_total = the framed size of all nb chunks.
+bool file_table_device(const uint64_t* d_payload_off, uint32_t nb, FileResult* d_results, uint32_t nfiles, uint64_t* d_total, hipStream_t s);
+
+// Decode side: one walker per file over d_streams[d_off[f], +d_size[f]) (count pass, exclusive
+// scan, emit pass), every record's header checked like bra_io_file_chunks_header_validate.
+// d_count[f] = the file's records, bit 31 set when its chain is rejected (empty stream, truncated or
+// overrunning record, invalid header: then only the records before the bad one are counted);
+// d_first[f] = its first record in d_hdr / d_payload_off (absolute offsets into d_streams);
+// d_status = {records of all files, header flag of k_unframe_headers, lowest rejected file or
+// UINT32_MAX}.  cap: capacity of d_hdr / d_payload_off, at least the sum of d_size[f] / 268.
+bool unframe_files_device(const uint8_t* d_streams, const uint64_t* d_off, const uint64_t* d_size, uint32_t nfiles, uint32_t cap,
+                          uint32_t max_chunk, uint8_t* d_hdr, uint64_t* d_payload_off, uint32_t* d_count, uint32_t* d_first,
+                          uint32_t* d_status, hipStream_t s);
 
 // Encoder output of up to MAX_SHARDS devices (headers, payload offsets, payloads; device memory of
 // the assembling device).  Global block g is part g % n's local block g / n with round_robin, else

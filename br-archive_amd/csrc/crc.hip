@@ -255,6 +255,141 @@ __global__ __launch_bounds__(CRC_TPB) void k_crc_stream(StreamArgs a, uint32_t n
     }
 }
 
+// ---- both CRCs of many files in one pass (files_plan.h) -------------------------------------------
+
+static_assert(FILES_PIECE == PIECE && FILES_HDR_MEM == CHUNK_HDR_MEM && FILES_HDR_DISK == CHUNK_HDR_DISK, "files_plan.h restates these");
+static_assert(FILES_WAVE_CHUNK <= 16 * 256, "a wave chunk's units are lined up with K[0..255]");
+
+struct FilesCrcArgs
+{
+    const uint8_t*   data;
+    const uint8_t*   hdr;     // 268-byte in-memory header of row b at hdr + 268 * b
+    const FileChunk* rows;
+    const FilePiece* pieces;  // 64 KiB pieces of the rows longer than FILES_WAVE_CHUNK
+    uint32_t*        res;     // FileResult records as dwords: chunks_crc at [8 f + 4], raw_crc at [8 f + 5]
+    uint32_t         nrows;
+    uint32_t         npieces;
+};
+
+// The segmented form of k_crc_stream: positions come from the chunk table instead of b * cs, and
+// every raw value goes to two result words of the chunk's file, moved by the distance to the end of
+// the file's chunk stream and of its plain stream.  Workgroups [0, npieces) take one 64 KiB piece of
+// a long chunk each; the workgroups after them take 4 table rows each, one per wave: the row's
+// header and, for a chunk of at most FILES_WAVE_CHUNK bytes, its data as well (a batch of small
+// files is mostly such chunks: a workgroup per chunk would spend sixteen rounds on a few units).
+__global__ __launch_bounds__(CRC_TPB) void k_crc_files(FilesCrcArgs a, uint32_t n_work)
+{
+    __shared__ uint32_t T[16][256];
+    __shared__ uint32_t S[4][256];
+    __shared__ uint32_t red[CRC_TPB / WAVE];
+    for (uint32_t i = threadIdx.x; i < 16 * 256; i += CRC_TPB)
+        (&T[0][0])[i] = (&c_crc.T[0][0])[i];
+    for (uint32_t i = threadIdx.x; i < 4 * 256; i += CRC_TPB)
+        (&S[0][0])[i] = (&c_crc.S[0][0])[i];
+    __syncthreads();
+    const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t % WAVE;
+    for (uint32_t w = blockIdx.x; w < n_work; w += gridDim.x)
+    {
+        if (w < a.npieces)
+        {
+            const FilePiece pc   = a.pieces[w];
+            const FileChunk row  = a.rows[pc.chunk];
+            const int64_t   pend = (int64_t) row.len - (int64_t) pc.after * PIECE;  // chunk-local piece end
+            if (pend <= 0)
+                continue;  // uniform (the plan lists no such piece)
+            const uint8_t* chunk = a.data + row.off;
+            const uint8_t* lo    = chunk + max<int64_t>(0, pend - (int64_t) PIECE);
+            uint32_t       acc   = 0;
+#pragma unroll 4
+            for (int i = 0; i < UNITS; ++i)
+            {
+                const int64_t u = pend - (int64_t) PIECE + 16 * (int64_t) (t + CRC_TPB * i);
+                acc             = shift_stride(acc, S);
+                if (u + 16 > 0)
+                    acc ^= crc16(load16(chunk + u, lo), T);
+            }
+            acc = mulmod(acc, c_crc.K[CRC_TPB - 1 - t]);
+            acc = wave_xor(acc);
+            if (lane == 0)
+                red[wv] = acc;
+            __syncthreads();
+            if (wv == 0)
+            {
+                uint32_t v = 0;
+#pragma unroll
+                for (int k = 0; k < CRC_TPB / WAVE; ++k)
+                    v ^= red[k];
+                const uint64_t after = (uint64_t) ((int64_t) row.len - pend);  // chunk bytes after the piece
+                const uint32_t fs    = wave_x8n(row.tail_stream + after);
+                const uint32_t fr    = wave_x8n(row.tail_raw + after);
+                if (lane == 0)
+                {
+                    atomicXor(a.res + 8ull * row.file + 4, mulmod(v, fs));
+                    atomicXor(a.res + 8ull * row.file + 5, mulmod(v, fr));
+                }
+            }
+            __syncthreads();
+        }
+        else
+        {
+            const uint32_t b = (w - a.npieces) * (CRC_TPB / WAVE) + wv;
+            if (b >= a.nrows)
+                continue;  // wave-uniform; no block barrier on this path
+            const FileChunk row  = a.rows[b];
+            const uint8_t*  h    = a.hdr + (uint64_t) b * CHUNK_HDR_MEM;
+            uint32_t        hacc = 0;
+            if (lane < HDR_UNITS)
+            {
+                const int u = (int) CHUNK_HDR_MEM - 16 * (HDR_UNITS - (int) lane);  // -4, 12, ..., 252
+                hacc        = mulmod(crc16(load16(h + u, h), T), c_crc.K[HDR_UNITS - 1 - lane]);
+            }
+            hacc             = wave_xor(hacc);
+            const bool small = row.len <= FILES_WAVE_CHUNK;
+            uint32_t   dacc  = 0;
+            if (small)
+            {
+                // units aligned to the chunk end, the first one ragged; unit j is followed by nu - 1 - j units
+                const uint8_t* chunk = a.data + row.off;
+                const uint32_t nu    = (row.len + 15u) / 16u;
+                for (uint32_t j = lane; j < nu; j += WAVE)
+                {
+                    const int64_t u = (int64_t) row.len - 16 * (int64_t) (nu - j);
+                    dacc ^= mulmod(crc16(load16(chunk + u, chunk), T), c_crc.K[nu - 1 - j]);
+                }
+                dacc = wave_xor(dacc);
+            }
+            const uint32_t fh = wave_x8n(row.tail_stream + row.len);
+            const uint32_t fs = wave_x8n(row.tail_stream);
+            const uint32_t fr = wave_x8n(row.tail_raw);
+            if (lane == 0)
+            {
+                atomicXor(a.res + 8ull * row.file + 4, mulmod(hacc, fh) ^ mulmod(dacc, fs));
+                if (small)
+                    atomicXor(a.res + 8ull * row.file + 5, mulmod(dacc, fr));
+            }
+        }
+    }
+}
+
+// One thread per file: where its records start and end in the framed output.
+__global__ void k_file_table(const uint64_t* __restrict__ poff, uint32_t nb, FileResult* __restrict__ res, uint32_t nfiles,
+                             uint64_t* __restrict__ total)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f == 0)
+        *total = poff[nb] + (uint64_t) CHUNK_HDR_DISK * nb;
+    if (f >= nfiles)
+        return;
+    FileResult     r     = res[f];
+    const uint32_t first = r.compressed, last = first + r.num_chunks;  // both <= nb
+    const uint64_t o0 = poff[first] + (uint64_t) CHUNK_HDR_DISK * first, o1 = poff[last] + (uint64_t) CHUNK_HDR_DISK * last;
+    const uint64_t len = r.size;
+    r.off              = o0;
+    r.size             = o1 - o0;
+    r.compressed       = (r.size < len) ? 1u : 0u;
+    res[f]             = r;
+}
+
 // ---- framing ------------------------------------------------------------------------------------
 
 // dst[0, n) = src[0, n): aligned 16-byte stores in the middle, byte stores at the two edges (so
@@ -341,6 +476,100 @@ __global__ __launch_bounds__(256) void k_unframe_headers(const uint8_t* __restri
                 atomicOr(status + 1, 2u);
         }
     }
+}
+
+// ---- per-file record walk (many files in one call) ----------------------------------------------
+
+// One file's record chain st[0, size): the number of whole, valid records before the end or the
+// first bad one, bit 31 set when the chain is rejected.  With poff, every counted record's payload
+// offset (base + its position) is written; both passes take the same decisions.
+__device__ uint32_t walk_file(const uint8_t* __restrict__ st, uint64_t size, uint32_t max_chunk, uint64_t base, uint64_t* __restrict__ poff)
+{
+    uint64_t pos = 0;
+    uint32_t n   = 0;
+    bool     bad = size == 0;
+    while (pos < size)
+    {
+        if (size - pos < CHUNK_HDR_DISK)
+        {
+            bad = true;
+            break;
+        }
+        const uint8_t* r  = st + pos;
+        const uint32_t pi = (uint32_t) r[0] | ((uint32_t) r[1] << 8) | ((uint32_t) r[2] << 16);
+        const uint32_t os = rd32(r + 3 + 256), es = rd32(r + 3 + 260);
+        if (pi >= max_chunk || es > max_chunk || os > max_chunk || es == 0 || os == 0 || es > size - pos - CHUNK_HDR_DISK)
+        {
+            bad = true;
+            break;
+        }
+        if (poff)
+            poff[n] = base + pos + CHUNK_HDR_DISK;
+        ++n;
+        pos += CHUNK_HDR_DISK + es;
+    }
+    return n | (bad ? 0x80000000u : 0u);
+}
+
+__global__ void k_files_count(const uint8_t* __restrict__ st, const uint64_t* __restrict__ off, const uint64_t* __restrict__ size,
+                              uint32_t nfiles, uint32_t max_chunk, uint32_t* __restrict__ count, uint32_t* __restrict__ status)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nfiles)
+        return;
+    const uint32_t c = walk_file(st + off[f], size[f], max_chunk, off[f], nullptr);
+    count[f]         = c;
+    if (c >> 31)
+        atomicMin(status + 2, f);
+}
+
+// One workgroup: exclusive scan of the record counts -> every file's first record; status[0] = total.
+__global__ __launch_bounds__(1024) void k_files_scan(const uint32_t* __restrict__ count, uint32_t nfiles, uint32_t* __restrict__ first,
+                                                     uint32_t* __restrict__ status)
+{
+    __shared__ uint32_t part_sum[1024 / WAVE];
+    __shared__ uint32_t carry_s;
+    if (threadIdx.x == 0)
+        carry_s = 0;
+    __syncthreads();
+    const int lane = lane_id(), w = threadIdx.x / WAVE;
+    for (uint32_t c0 = 0; c0 < nfiles; c0 += 1024)
+    {
+        const uint32_t f = c0 + threadIdx.x;
+        const uint32_t v = f < nfiles ? count[f] & 0x7FFFFFFFu : 0u;
+        const uint32_t x = wave_scan<true>(v, 0u, OpAdd());
+        if (lane == WAVE - 1)
+            part_sum[w] = x;
+        __syncthreads();
+        uint32_t before = carry_s, all = 0;
+        for (int k = 0; k < 1024 / WAVE; ++k)
+        {
+            if (k < w)
+                before += part_sum[k];
+            all += part_sum[k];
+        }
+        if (f < nfiles)
+            first[f] = before + x - v;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            carry_s += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        status[0] = carry_s;
+}
+
+__global__ void k_files_emit(const uint8_t* __restrict__ st, const uint64_t* __restrict__ off, const uint64_t* __restrict__ size,
+                             uint32_t nfiles, uint32_t max_chunk, const uint32_t* __restrict__ count, const uint32_t* __restrict__ first,
+                             uint32_t cap, uint64_t* __restrict__ poff)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nfiles)
+        return;
+    // (the same walk as the count pass found count[f] records: they fit below cap, which the host
+    // sized from the stream sizes; checked all the same)
+    if ((uint64_t) first[f] + (count[f] & 0x7FFFFFFFu) <= cap)
+        (void) walk_file(st + off[f], size[f], max_chunk, off[f], poff + first[f]);
 }
 
 // ---- assembly of sharded encoder output ---------------------------------------------------------
@@ -536,6 +765,53 @@ bool unframe_chunks_device(const uint8_t* d_stream, uint64_t size, uint32_t cap,
     if (cap)
     {
         hipLaunchKernelGGL(k_unframe_headers, dim3(std::min<uint32_t>(cap, 65535)), dim3(256), 0, s, d_stream, d_payload_off, cap, max_chunk,
+                           d_hdr, d_status);
+        BRA_HIP_CHECK(hipGetLastError());
+    }
+    return true;
+}
+
+uint32_t crc_files_init(uint64_t V) { return ~mulmod(0xFFFFFFFFu, crc_x8n(V)); }
+
+bool crc_files_device(const uint8_t* d_data, const uint8_t* d_hdr, const FileChunk* d_rows, uint32_t nrows, const FilePiece* d_pieces,
+                      uint32_t npieces, FileResult* d_results, hipStream_t s)
+{
+    if (nrows == 0)
+        return true;
+    if (!d_data || !d_hdr || !d_rows || !d_results || (npieces && !d_pieces))
+        return false;
+    const uint64_t n_work = (uint64_t) npieces + (nrows + CRC_TPB / WAVE - 1) / (CRC_TPB / WAVE);
+    if (n_work >= (1ull << 31))
+        return false;
+    FilesCrcArgs a{d_data, d_hdr, d_rows, d_pieces, reinterpret_cast<uint32_t*>(d_results), nrows, npieces};
+    hipLaunchKernelGGL(k_crc_files, dim3((uint32_t) std::min<uint64_t>(n_work, 1u << 20)), dim3(CRC_TPB), 0, s, a, (uint32_t) n_work);
+    BRA_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+bool file_table_device(const uint64_t* d_payload_off, uint32_t nb, FileResult* d_results, uint32_t nfiles, uint64_t* d_total, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_file_table, dim3(div_up(std::max(nfiles, 1u), 256u)), dim3(256), 0, s, d_payload_off, nb, d_results, nfiles, d_total);
+    BRA_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+bool unframe_files_device(const uint8_t* d_streams, const uint64_t* d_off, const uint64_t* d_size, uint32_t nfiles, uint32_t cap,
+                          uint32_t max_chunk, uint8_t* d_hdr, uint64_t* d_payload_off, uint32_t* d_count, uint32_t* d_first,
+                          uint32_t* d_status, hipStream_t s)
+{
+    if (nfiles == 0)
+        return false;
+    BRA_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), 0, 2, s));
+    BRA_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status + 2), -1, 1, s));  // no file rejected
+    const uint32_t g = div_up(nfiles, 64u);
+    hipLaunchKernelGGL(k_files_count, dim3(g), dim3(64), 0, s, d_streams, d_off, d_size, nfiles, max_chunk, d_count, d_status);
+    hipLaunchKernelGGL(k_files_scan, dim3(1), dim3(1024), 0, s, d_count, nfiles, d_first, d_status);
+    hipLaunchKernelGGL(k_files_emit, dim3(g), dim3(64), 0, s, d_streams, d_off, d_size, nfiles, max_chunk, d_count, d_first, cap, d_payload_off);
+    BRA_HIP_CHECK(hipGetLastError());
+    if (cap)
+    {
+        hipLaunchKernelGGL(k_unframe_headers, dim3(std::min<uint32_t>(cap, 65535)), dim3(256), 0, s, d_streams, d_payload_off, cap, max_chunk,
                            d_hdr, d_status);
         BRA_HIP_CHECK(hipGetLastError());
     }

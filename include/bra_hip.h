@@ -315,3 +315,8 @@ int bra_gpu_selftest(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- Part 5: many files in one call ----------------------------------------------------------- */
+/* Compress or decompress a whole list of files of any sizes in one device call, with a per-file
+ * result table: declared in bra_hip_files.h. */
+#include "bra_hip_files.h"

@@ -227,12 +227,19 @@ def bwt_encode(buf: bytes):
     return bytes(out)[:n], pi.value
 
 
-def bwt_decode(buf: bytes, primary_index: int) -> bytes:
-    """bra_bwt_decode2."""
+def bwt_decode(buf: bytes, primary_index: int, want_transform: bool = False):
+    """bra_bwt_decode2.  want_transform: pass a transform buffer as the reference's callers do and
+    return (decoded bytes, transform as a numpy uint32 array of len(buf) entries)."""
     n = len(buf)
     out = (C.c_uint8 * max(1, n))()
-    lib.bra_bwt_decode2(_buf(buf), n, primary_index, None, out)
-    return bytes(out)[:n]
+    if not want_transform:
+        lib.bra_bwt_decode2(_buf(buf), n, primary_index, None, out)
+        return bytes(out)[:n]
+    import numpy as np
+
+    tr = np.zeros(max(1, n), np.uint32)
+    lib.bra_bwt_decode2(_buf(buf), n, primary_index, tr.ctypes.data_as(C.POINTER(C.c_uint32)), out)
+    return bytes(out)[:n], tr[:n]
 
 
 def mtf_encode(buf: bytes):
@@ -691,6 +698,21 @@ class BlockCodec:
         if f(self.ctx, C.byref(p), C.byref(b)) != 0:
             raise RuntimeError("bra_gpu_debug_bwt_path failed")
         return int(p.value), int(b.value)
+
+    IBWT_PATHS = ("none", "main", "two_walk", "fallback")
+    IBWT_WALKS = ("one", "two", "one_if")
+
+    def debug_ibwt_path(self) -> dict:
+        """The last decode's inverse BWT (bra_gpu_debug_ibwt_path): dict(path, walk, pool_used,
+        pool_cap) with path one of IBWT_PATHS ("fallback": the main path ran out of overflow
+        chunks and the two-walk path redid the batch) and walk one of IBWT_WALKS ("one_if": one
+        step per load because a block of the batch did not suit the two-step walk)."""
+        f = lib.bra_gpu_debug_ibwt_path
+        f.argtypes, f.restype = [C.c_void_p] + [C.POINTER(C.c_uint)] * 4, C.c_int
+        p, w, u, k = C.c_uint(0), C.c_uint(0), C.c_uint(0), C.c_uint(0)
+        if f(self.ctx, C.byref(p), C.byref(w), C.byref(u), C.byref(k)) != 0:
+            raise RuntimeError("bra_gpu_debug_ibwt_path failed")
+        return dict(path=self.IBWT_PATHS[p.value], walk=self.IBWT_WALKS[w.value], pool_used=int(u.value), pool_cap=int(k.value))
 
     def stage_ptr(self, stage: int) -> int:
         return lib.bra_gpu_stage_ptr(self.ctx, stage) or 0

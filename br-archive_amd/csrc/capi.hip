@@ -1574,6 +1574,23 @@ int bra_gpu_debug_bwt_path(bra_gpu_ctx_t* c, unsigned* path, unsigned* max_bins)
     return 0;
 }
 
+// Diagnostics: what the last inverse BWT on the context did (ibwt.h: IB_PATH_*, IB_WALK_*) and how
+// many overflow chunks its walk claimed out of how many.
+int bra_gpu_debug_ibwt_path(bra_gpu_ctx_t* c, unsigned* path, unsigned* walk, unsigned* pool_used, unsigned* pool_cap)
+{
+    if (!c || !path || !walk || !pool_used || !pool_cap)
+        return -1;
+    DevGuard dg(c->device);
+    uint32_t p = 0, m = 0, u = 0, k = 0;
+    if (!ibwt_last_path(c->ib, &p, &m, &u, &k))
+        return -1;
+    *path      = p;
+    *walk      = m;
+    *pool_used = u;
+    *pool_cap  = k;
+    return 0;
+}
+
 const char* bra_gpu_version(void) { return "bra_hip 0.1.0 (gfx950)"; }
 
 void bra_gpu_prof_enable(bra_gpu_ctx_t* c, uint64_t mask)

@@ -1139,6 +1139,9 @@ bool ibwt_device(IbwtWorkspace& w, const uint8_t* d_L, const uint32_t* d_pi, con
     BRA_HIP_CHECK(hipMemsetAsync(w.nopair, 0, 4, s));
     hipLaunchKernelGGL(k_ib_scan, dim3(std::min<uint32_t>(nblocks, 65535)), dim3(TPB), 0, s, w.tiling.d_first, w.tiling.d_count, nblocks, w.th,
                        w.nopair);
+    w.last_path = main_path ? IB_PATH_MAIN : IB_PATH_TWO_WALK;
+    w.last_pair = false;
+    w.last_used = w.last_cap = 0;
     if (!main_path)
         return ibwt_two_walk(w, d_L, d_pi, d_blocks, nblocks, d_out, s);
 
@@ -1233,8 +1236,26 @@ bool ibwt_device(IbwtWorkspace& w, const uint8_t* d_L, const uint32_t* d_pi, con
     uint32_t used = 0;
     BRA_HIP_CHECK(hipMemcpyAsync(&used, w.ctl + 300, 4, hipMemcpyDeviceToHost, s));
     BRA_HIP_CHECK(hipStreamSynchronize(s));
+    w.last_pair = w.pair;
+    w.last_used = used;
+    w.last_cap  = w.pool_cap;
     if (used > w.pool_cap)
+    {
+        w.last_path = IB_PATH_FALLBACK;
         return ibwt_two_walk(w, d_L, d_pi, d_blocks, nblocks, d_out, s);
+    }
+    return true;
+}
+
+bool ibwt_last_path(const IbwtWorkspace& w, uint32_t* path, uint32_t* walk, uint32_t* pool_used, uint32_t* pool_cap)
+{
+    uint32_t nopair = 0;
+    if (w.last_path != IB_PATH_NONE && w.last_pair)
+        BRA_HIP_CHECK(hipMemcpy(&nopair, w.nopair, 4, hipMemcpyDeviceToHost));
+    *path      = w.last_path;
+    *walk      = !w.last_pair ? IB_WALK_ONE : nopair ? IB_WALK_ONE_IF : IB_WALK_TWO;
+    *pool_used = w.last_used;
+    *pool_cap  = w.last_cap;
     return true;
 }
 

@@ -20,6 +20,18 @@ extern "C" {
  */
 int bra_gpu_debug_bwt_path(bra_gpu_ctx_t* ctx, unsigned* path, unsigned* max_bins);
 
+/*
+ * The last inverse BWT on the context (a batch decode; call it after that call has returned).
+ * *path: 0 none yet, 1 the main path (splitter walk staged in slots and overflow chunks), 2 the
+ * two-walk path chosen directly (a block of 2^24 bytes or more), 3 the main path followed by the
+ * two-walk fallback because the overflow pool ran out.  *walk, for paths 1 and 3: 0 one transform
+ * step per load, 1 two steps per load, 2 one step because a block of the batch did not suit pairs
+ * (read from the device by this call); 0 for path 2.  *pool_used: 256-byte overflow chunks the walk
+ * asked for (it keeps counting past the capacity); *pool_cap: chunks the pool held.  Both 0 for
+ * path 2.  Returns 0, -1 on a null argument or a failed device read.
+ */
+int bra_gpu_debug_ibwt_path(bra_gpu_ctx_t* ctx, unsigned* path, unsigned* walk, unsigned* pool_used, unsigned* pool_cap);
+
 #ifdef __cplusplus
 }
 #endif
